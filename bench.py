@@ -3,8 +3,15 @@ BEV tensors of the constants.py grid — BASELINE.json metric "BEV samples/sec (
 IntentNetViT at 1/2/4/8 MI355X; attn MFMA util %", config 2 (bf16, batch 8 per GPU) at
 N=1 and config 3 (DDP over RCCL) for N>1.
 
-    python bench.py [--gpus N --steps K --warmup W]
+    python bench.py [--gpus N --steps K --warmup W] [--dump-outputs DIR] [--full]
     torchrun --nproc-per-node N --master-addr 127.0.0.1 bench.py --gpus N ...
+
+A plain run sets up, warms up, times the K steps and prints the line. ``--full`` adds the legs that
+take runs or lookups of their own: the attention kernel alone at the bench shape
+(``roofline.isolated``), the CPU baseline (``cpu_baseline``) and the comparison with the committed
+profiles (``roofline.traffic`` / ``frac_rocprof``). ``--dump-outputs DIR`` writes what the last timed
+step computed as ``DIR/<name>.npy`` (dump_outputs); the inputs and weights are seeded, so two
+builds run with the same arguments can be compared output for output.
 
 Without torchrun's environment, ``--gpus N > 1`` starts the N ranks itself (child processes with
 RANK / LOCAL_RANK / WORLD_SIZE set, started before this process touches the GPU) and exits with
@@ -265,6 +272,61 @@ def cpu_baseline(steps=3):
             "step_s": med, "steps_s": [round(t, 3) for t in ts]}
 
 
+DUMP_CAP_BYTES = 64 * 2 ** 20  # --dump-outputs: upper bound for the whole directory
+
+
+def sample_f32(t, cap, seed=0):
+    """``t`` flattened as f32 on the host; more than ``cap`` elements: the elements at ``cap`` fixed
+    positions (sorted draw without replacement from a generator seeded by ``seed`` and the size), the
+    same positions in every run."""
+    t = t.detach().reshape(-1)
+    if t.numel() > cap:
+        g = torch.Generator().manual_seed(seed * 1000003 + t.numel())
+        idx = torch.randperm(t.numel(), generator=g)[:cap].sort().values
+        t = t.index_select(0, idx.to(t.device))
+    return t.float().cpu()
+
+
+def dump_outputs(path, arrays):
+    """Write {name: tensor} as path/<name>.npy (float32); refuses more than DUMP_CAP_BYTES in all."""
+    import numpy as np
+    arrays = {k: np.ascontiguousarray(v.detach().float().cpu().numpy()) for k, v in arrays.items()}
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_CAP_BYTES:
+        raise RuntimeError(f"--dump-outputs: {total} bytes exceed the {DUMP_CAP_BYTES}-byte bound")
+    os.makedirs(path, exist_ok=True)
+    for k, a in arrays.items():
+        np.save(os.path.join(path, k + ".npy"), a)
+    return total
+
+
+def train_outputs(d, model, per_param=4096):
+    """What the last Trainer.step handed back and left behind: the loss dict it returned, and a fixed
+    sample (<= per_param elements of every parameter, in named_parameters order) of the gradients
+    its backward produced and of the weights its optimizer step wrote."""
+    out = {k: v.detach().reshape(()) for k, v in d.items()}
+    grads, params = [], []
+    for i, (_, p) in enumerate(model.named_parameters()):
+        params.append(sample_f32(p, per_param, seed=i))
+        g = p.grad if p.grad is not None else torch.zeros_like(p)
+        grads.append(sample_f32(g, per_param, seed=i))
+    out["grad_sample"] = torch.cat(grads)
+    out["param_sample"] = torch.cat(params)
+    return out
+
+
+def eval_outputs(logits, preds, cap=2 ** 21):
+    """The last eval step's results: the model's three output maps (a fixed sample of <= cap elements
+    each) and the post-processed predictions of that batch (kept boxes of all samples concatenated,
+    ``pred_counts`` the number per sample)."""
+    out = {n: sample_f32(t, cap, seed=i) for i, (n, t) in
+           enumerate(zip(("cls_logits", "box_preds", "intent_logits"), logits))}
+    out["pred_counts"] = torch.tensor([float(p["pred_scores"].numel()) for p in preds])
+    for k in ("pred_scores", "pred_boxes_xywha", "pred_intentions"):
+        out[k] = torch.cat([p[k].detach().float().cpu() for p in preds]) if preds else torch.zeros(0)
+    return out
+
+
 def visible_gpus():
     """GPUs this process may use, counted without initialising HIP: torch.cuda.device_count() reads
     the device count without creating a context on this image — checked here, because the parent
@@ -373,6 +435,14 @@ def main():
                     help="N=1 train mode: also time the bucketed RCCL path (a world-1 process group, "
                          "Trainer(force_buckets=True): comm stream, per-parameter events, the all-reduces) "
                          "right after the plain step in the same process; both go into the line")
+    ap.add_argument("--dump-outputs", type=str, default=None, metavar="DIR",
+                    help="after the timed steps, write what the last one computed as DIR/<name>.npy (float32, "
+                         "<= 64 MB in all): train: the returned loss dict, and a fixed sample of the gradients and "
+                         "of the updated weights; eval: the model outputs (sampled) and the kept predictions")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline figure does not need: the isolated attention leg, the CPU "
+                         "baseline, the lookups in the committed profiles (--no-isolated / --no-cpu-baseline "
+                         "still leave one out)")
     args = ap.parse_args()
     if args.gpus < 1:
         sys.exit("bench.py: --gpus must be >= 1")
@@ -463,14 +533,19 @@ def main():
         # next batch's forward (utils.PostPipeline); flush() before and at the end of the timed
         # region, so it holds exactly `steps` forwards and `steps` post-processings
         pipe = utils.PostPipeline(anchors, 0.1, 0.2)
+        last = {}  # --dump-outputs: the newest batch's model outputs and predictions
 
         def collect(preds):
             if preds is not None:
                 kept.append(sum(int(p["pred_scores"].numel()) for p in preds))
+                if args.dump_outputs:
+                    last["preds"] = preds
 
         def step():  # eval_vit.py:144-180: forward, sigmoid >= 0.1, decode, NMS(0.2), argmax intention
             with torch.inference_mode():
                 cls, box, it = model(batch["lidar_bev"], batch["map_bev"])
+                if args.dump_outputs:
+                    last["logits"] = (cls, box, it)
                 collect(pipe.push(cls, box, it))
             return {"loss": torch.zeros(())}
 
@@ -503,6 +578,10 @@ def main():
     attn_ms = {k: kexec[k][0] for k in ATTN}
     attn_n = {k: kexec[k][2] for k in ATTN}
     ops.KernelTimer.enabled = set()
+    if args.dump_outputs and rank == 0:
+        with torch.inference_mode():
+            dump_outputs(args.dump_outputs, train_outputs(d, model) if train
+                         else eval_outputs(last["logits"], last["preds"]))
     if world > 1:
         t = torch.tensor([el], device=dev)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
@@ -523,7 +602,7 @@ def main():
     achieved = afl / (attn_ms[roof] * 1e-3) / 1e12 if attn_n[roof] else float("nan")
     # PMC traffic was collected on the default train configuration only
     default_cfg = train and (H, W) == (400, 720) and B == 8 and cd == torch.bfloat16 and not args.augment
-    traffic, traffic_src = pmc_traffic(ATTN[roof]["kernels"]) if default_cfg else (None, None)
+    traffic, traffic_src = pmc_traffic(ATTN[roof]["kernels"]) if default_cfg and args.full else (None, None)
     # attention MFMA utilisation (BASELINE metric "attn MFMA util %"): attention fwd + bwd algorithmic
     # flops per step / their measured kernel time per step; ViT attention + MLP block flops per step /
     # the whole step's wall time (a lower bound for the blocks' own utilisation)
@@ -564,7 +643,8 @@ def main():
                      "traffic_note": (f"HBM bytes per launch from {traffic_src} (rocprofv3 FETCH_SIZE x2 + WRITE_SIZE, "
                                       f"gfx950-corrected, summed over the kernels); algorithmic bytes "
                                       f"{attn_bytes(roof, B, N, 6):.4g}")
-                     if traffic is not None else "no PMC summary for this configuration",
+                     if traffic is not None else ("no PMC summary for this configuration" if args.full else
+                                                  "looked up in the committed PMC summary with --full"),
                      "per_step_ms": {k: round(v, 3) for k, v in per_step.items()}},
         "attn_mfma_util": {
             "attention_fwd_bwd": round(at_fl / (at_ms * 1e-3) / 1e12 / peak, 4) if at_ms else None,
@@ -576,7 +656,7 @@ def main():
                       "frac": round(fl_step / (el / args.steps) / 1e12 / peak, 4),
                       "flops_per_step_per_gpu": fl_step},
     }
-    if default_cfg:
+    if default_cfg and args.full:
         # the same launches' device time from a committed rocprofv3 kernel trace of the profiled
         # bench command (tools/kunion.py --json): the figure the profile files reproduce
         us, src, gen = rocprof_union(roof)
@@ -589,7 +669,7 @@ def main():
                                                     f"the profiler lowers the clock, MI355X_MICROARCH.md DVFS item 2)")
     if args.intervals_out and timing:
         out["roofline"]["intervals_file"] = os.path.relpath(os.path.abspath(args.intervals_out), HERE)
-    if default_cfg and world == 1 and not args.no_isolated:
+    if default_cfg and world == 1 and args.full and not args.no_isolated:
         # the same kernel(s) alone on the same shape (outside the timed region): the frac without the
         # other ViT stream's kernels sharing the CUs
         iso, reps = isolated_attn_ms(roof, B, N, 6, dev)
@@ -606,7 +686,7 @@ def main():
         out["loss"] = loss_v
     else:
         out["kept_boxes_per_step"] = kept[-1] if kept else 0
-    if rank == 0 and world == 1 and train and not args.no_cpu_baseline:
+    if rank == 0 and world == 1 and train and args.full and not args.no_cpu_baseline:
         out["cpu_baseline"] = cpu_baseline()
     if rank == 0:
         print(json.dumps(out), flush=True)

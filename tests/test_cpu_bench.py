@@ -47,6 +47,32 @@ def test_visible_gpus_does_not_initialise_hip():
     assert n >= 0 and not torch.cuda.is_initialized()
 
 
+def test_sample_is_fixed_and_dump_writes_f32_within_the_bound(tmp_path, monkeypatch):
+    """--dump-outputs helpers: the sample takes the same sorted positions every time (and all of a
+    small tensor), the files are float32 under their names, and the size bound is enforced."""
+    import numpy as np
+    import torch
+    t = torch.arange(10000, dtype=torch.float64)
+    a, b = bench.sample_f32(t, 100, seed=3), bench.sample_f32(t, 100, seed=3)
+    assert a.dtype == torch.float32 and a.shape == (100,) and torch.equal(a, b)
+    assert bool((a[1:] > a[:-1]).all()) and not torch.equal(a, bench.sample_f32(t, 100, seed=4))
+    assert torch.equal(bench.sample_f32(t[:50].reshape(5, 10), 100), t[:50].float())
+    n = bench.dump_outputs(str(tmp_path / "o"), {"loss": torch.tensor(1.5, requires_grad=True),
+                                                 "num_pos_anchors": torch.tensor(7), "grad_sample": a})
+    assert n == 4 + 4 + 400
+    got = {f: np.load(tmp_path / "o" / f) for f in sorted(os.listdir(tmp_path / "o"))}
+    assert sorted(got) == ["grad_sample.npy", "loss.npy", "num_pos_anchors.npy"]
+    assert all(v.dtype == np.float32 for v in got.values())
+    assert got["loss.npy"] == 1.5 and got["num_pos_anchors.npy"] == 7.0
+    assert np.array_equal(got["grad_sample.npy"], a.numpy())
+    monkeypatch.setattr(bench, "DUMP_CAP_BYTES", 399)
+    try:
+        bench.dump_outputs(str(tmp_path / "p"), {"grad_sample": a})
+        raise AssertionError("the size bound was not enforced")
+    except RuntimeError:
+        assert not (tmp_path / "p").exists()
+
+
 class _FakeOps:
     """ops.ktime_read stand-in: per tag, (start_ms, stop_ms) relative to the first launch."""
     rec = {0: [(0.0, 0.3)], 1: [(1.0, 1.5), (1.2, 1.6)], 2: [(1.5, 2.1), (1.6, 2.4)]}
