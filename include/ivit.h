@@ -452,6 +452,44 @@ int ivit_im2col(int x_dtype, const void* X, long B, long H, long W, long C, long
 int ivit_col2im(const float* dcols, long ldc, long B, long H, long W, long C, long k, long stride, long pad, long Ho,
                 long Wo, float* dX, void* stream);
 
+/* ---- Heuristic intention labels (heuristic_labeling.py:10-124 get_vehicle_intention_heuristic_enhanced,
+ * applied to every row by preprocess_intent_labels.py:41-57) ---------------------------------
+ * The reference filters and sorts the whole annotation table once per row; this labels all rows
+ * of one or more logs in one launch, one thread per row. Rows are concatenated and sorted by
+ * (track, timestamp_ns), unique within a track: ts [n] int64, xy [n, 2] f64 (tx_m, ty_m), quat
+ * [n, 4] f64 (qx, qy, qz, qw), is_vehicle [n] u8 (category in VEHICLE_CATEGORIES,
+ * preprocess_intent_labels.py:42); track t owns rows track_off[t] .. track_off[t+1]-1 (int64,
+ * n_tracks + 1 entries, track_off[0] = 0, track_off[n_tracks] = n). All device pointers; params
+ * is a HOST pointer (constants.py values, passed to the kernel by value).
+ * intent [n] int32: -1 for a non-vehicle row, else INTENTIONS_MAP (constants.py), OTHER = 7 by
+ * default. The future rows (:37) are the min(horizon_steps, rows left in the track) rows after
+ * the row; fewer than min_future_points -> OTHER (:38). With the last of them as the end row:
+ * dist = |xy_end - xy|, speed = dist / ((double)(ts_end - ts) * 1e-9 + 1e-9) (:40-45); a zero-norm
+ * quaternion at either row -> OTHER (:47-52, before the speed test); dh = atan2(sin, cos) of the
+ * yaw difference (:50-51); speed < stopped_speed -> PARKED if dist < parked_max_disp else
+ * STOPPING_STOPPED (:54-55); speed >= moving_speed: dh > turn_heading TURN_LEFT, dh < -turn_heading
+ * TURN_RIGHT (:79-81), keep_heading < |dh| < turn_heading LEFT_/RIGHT_CHANGE_LANE by the sign of
+ * dh (:86-88), |dh| <= keep_heading KEEP_LANE if the displacement's component across the current
+ * heading is < keep_lane_max_lat (:118-122). f64 throughout, no contraction.
+ * yaw [n] f64: the z angle of scipy's extrinsic as_euler('xyz') of the normalised quaternion,
+ * atan2(2(wz + xy), 1 - 2(y^2 + z^2)) (exact away from gimbal lock); 0 for a zero norm.
+ * MAP CONTEXT IS NOT IMPLEMENTED: this is the reference's map-free branch, what it computes when
+ * av2 is not importable (AV2_MAP_AVAILABLE false / static_map None): no intersection test
+ * (:61-77, :83-84) and no lane-polygon containment (:93-117). n = 0 succeeds without a launch. */
+typedef struct ivit_label_params {
+  int horizon_steps;        /* INTENTION_HORIZON_STEPS */
+  int min_future_points;    /* 5 (heuristic_labeling.py:16) */
+  double stopped_speed;     /* MIN_SPEED_STOPPED */
+  double moving_speed;      /* MIN_SPEED_MOVING */
+  double turn_heading;      /* HEADING_CHANGE_THRESH_TURN (rad) */
+  double keep_heading;      /* HEADING_CHANGE_THRESH_LANE_KEEP (rad) */
+  double parked_max_disp;   /* PARKED_MAX_DISP_M */
+  double keep_lane_max_lat; /* KEEP_LANE_MAX_LAT_DIST_FALLBACK */
+} ivit_label_params;
+int ivit_intent_labels(const long* ts, const double* xy, const double* quat, const unsigned char* is_vehicle,
+                       const long* track_off, long n, long n_tracks, const ivit_label_params* params, int* intent,
+                       double* yaw, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -5,7 +5,9 @@ Checkpoint → model (same cfg defaults as eval_vit.py:72-84) → anchors → ba
 confidence threshold 0.1, decode, NMS(0.2), argmax intention → detection mAP at
 DETECTION_IOU_THRESHOLDS and intention accuracy / F1 on matched detections.
 
-Differences, none in the numerics: ``--synthetic`` evaluates seeded synthetic BEV batches
+Differences, none in the numerics: without ``--synthetic`` the Argoverse-2 logs under
+``--data-dir`` (VAL_DATA_DIR by default) are evaluated through dataset.FrameBatchLoader, rasters
+built on the GPU, on the constants.py grid only; ``--synthetic`` evaluates seeded synthetic BEV batches
 (random-init weights when no checkpoint exists, which makes every anchor pass the threshold
 — the worst case for NMS); checkpoints load with ``torch.load(weights_only=True)`` (the
 pickled ``BasicBlock`` class in ``backbone_cfg`` is allow-listed by name); post-processing runs
@@ -23,7 +25,8 @@ import torch
 
 import model_vit
 from constants import (ANCHOR_CONFIGS_PAPER, DETECTION_IOU_THRESHOLDS, EVAL_USE_ROTATED_IOU, GRID_HEIGHT_PX,
-                       GRID_WIDTH_PX, INTENTIONS_MAP_REV, IOU_THRESHOLD_FOR_INTENTION_MATCH, LIDAR_TOTAL_CHANNELS,
+                       GRID_WIDTH_PX, INTENTIONS_MAP_REV, IOU_THRESHOLD_FOR_INTENTION_MATCH, LIDAR_SWEEPS,
+                       LIDAR_TOTAL_CHANNELS,
                        MAP_CHANNELS, NUM_INTENTION_CLASSES)
 from metrics import detection_map_device as detection_map, intention_matches_device as intention_matches
 from model_vit import IntentNetViT
@@ -66,6 +69,8 @@ def default_cfg(cfg: dict, grid):
 def parse_args(argv=None):
     ap = argparse.ArgumentParser(description=__doc__.splitlines()[0])
     ap.add_argument("--synthetic", action="store_true")
+    ap.add_argument("--data-dir", type=str, default=VAL_DATA_DIR, help="Argoverse-2 sensor split to evaluate")
+    ap.add_argument("--num-sweeps", type=int, default=LIDAR_SWEEPS, help="LiDAR sweeps per sample (dataset.py:158)")
     ap.add_argument("--checkpoint", type=str, default=None)
     ap.add_argument("--batch", type=int, default=INFERENCE_BATCH_SIZE)
     ap.add_argument("--batches", type=int, default=4, help="synthetic batches")
@@ -151,10 +156,15 @@ def main_eval_vit(argv=None, variant="vit"):
         loader = SyntheticBEVLoader(args.batch, args.batches, img_size, rank=0, device=device,
                                     resident=False)
     else:
-        if not Path(VAL_DATA_DIR).is_dir():
-            print(f"ERROR: Evaluation data directory not found: {VAL_DATA_DIR} (use --synthetic)")
+        if not Path(args.data_dir).is_dir():
+            print(f"ERROR: Evaluation data directory not found: {args.data_dir} (use --synthetic)")
             return 1
-        raise SystemExit("The Argoverse-2 dataset loader is outside this build's scope; use --synthetic")
+        if (H, W) != (GRID_HEIGHT_PX, GRID_WIDTH_PX) or tuple(img_size) != (GRID_HEIGHT_PX, GRID_WIDTH_PX):
+            raise SystemExit(f"--grid {args.grid} / checkpoint img_size {tuple(img_size)}: Argoverse-2 rasters have "
+                             f"the constants.py grid {GRID_HEIGHT_PX}x{GRID_WIDTH_PX}; other grids need --synthetic")
+        from dataset import ArgoverseIntentNetDataset, FrameBatchLoader  # pandas / pyarrow only in this mode
+        val_set = ArgoverseIntentNetDataset(args.data_dir, num_sweeps=args.num_sweeps, is_train=False, device=device)
+        loader = FrameBatchLoader(val_set, args.batch, shuffle=False, device=device)
 
     if variant == "vit":
         stride = int(cfg.get('vit_model_name_lidar', 'vit_small_patch8_224').split('_patch')[-1].split('_')[0]) \

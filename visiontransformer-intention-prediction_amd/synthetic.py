@@ -6,7 +6,8 @@ Distribution: LiDAR occupancy U[0,1), map rasters Bernoulli(0.1
 G=20 boxes per sample with cx~U[-20,60)·s, cy~U[-72,72)·s (s = H/400, so the 2x grid of
 config 5 doubles the ranges), w~U[1.5,3.0), l~U[3.5,6.5), yaw~U[-pi,pi), intentions~U{0..7}.
 Seeded by ``torch.Generator('cpu').manual_seed(1234 + rank)`` so every DDP rank draws its
-own shard. The Argoverse-2 loader (dataset.py) is outside this build's scope.
+own shard. Real Argoverse-2 logs go through dataset.FrameBatchLoader, which yields the same
+format (train_vit.py / eval_vit.py without ``--synthetic``).
 """
 from __future__ import annotations
 

@@ -6,8 +6,11 @@ same per-batch NaN skips and the same checkpoint dict ({'epoch', 'model_state_di
 'optimizer_state_dict', 'backbone_cfg'}). Differences, all outside the numerics:
 
 * ``--synthetic`` feeds seeded synthetic BEV batches of the constants.py grid (synthetic.py);
-  without it the script looks for TRAIN_DATA_DIR exactly like the reference and stops if it
-  is missing (the Argoverse-2 loader is outside this build's scope, SURVEY.md §8f);
+  without it the script trains on the Argoverse-2 logs under ``--data-dir`` (TRAIN_DATA_DIR by
+  default, and the reference's stop when it is missing): dataset.ArgoverseIntentNetDataset and
+  a FrameBatchLoader build every batch's rasters on the GPU (``--augment`` included), rank r
+  takes every world-th sequence; real rasters have the constants.py grid, so another ``--grid``
+  is refused; the logs need annotations_with_intent.feather (preprocess_intent_labels.py);
 * data parallel: run under ``torchrun --nproc-per-node N`` — one process per GPU, gradients
   all-reduced over RCCL in buckets overlapped with backward (ddp.py); rank r draws synthetic
   shard 1234 + r; only rank 0 prints and saves;
@@ -25,8 +28,8 @@ from pathlib import Path
 import torch
 
 from constants import (ANCHOR_CONFIGS_PAPER, DOMINANT_CLASSES_FOR_DOWNSAMPLING, GRID_HEIGHT_PX, GRID_WIDTH_PX,
-                       INTENTION_DOWNSAMPLE_RATIO, LIDAR_TOTAL_CHANNELS, MAP_CHANNELS)
-from ddp import all_reduce_sum, init_distributed
+                       INTENTION_DOWNSAMPLE_RATIO, LIDAR_SWEEPS, LIDAR_TOTAL_CHANNELS, MAP_CHANNELS)
+from ddp import all_reduce_sum, any_rank, init_distributed
 from loss import DetectionIntentionLoss
 from model_vit import BasicBlock, IntentNetViT
 from optim import FusedAdamW
@@ -86,6 +89,8 @@ def cnn_backbone_cfg():
 def parse_args(argv=None):
     ap = argparse.ArgumentParser(description=__doc__.splitlines()[0])
     ap.add_argument("--synthetic", action="store_true", help="seeded synthetic BEV batches instead of TRAIN_DATA_DIR")
+    ap.add_argument("--data-dir", type=str, default=TRAIN_DATA_DIR, help="Argoverse-2 sensor split to train on")
+    ap.add_argument("--num-sweeps", type=int, default=LIDAR_SWEEPS, help="LiDAR sweeps per sample (dataset.py:158)")
     ap.add_argument("--epochs", type=int, default=NUM_EPOCHS)
     ap.add_argument("--batches-per-epoch", type=int, default=16, help="synthetic batches per epoch")
     ap.add_argument("--batch", type=int, default=TRAIN_BATCH_SIZE, help="per-GPU batch")
@@ -98,6 +103,18 @@ def parse_args(argv=None):
     ap.add_argument("--augment", action="store_true",
                     help="training-time augment_bev on every batch (dataset.py:352-353), on the GPU")
     return ap.parse_args(argv)
+
+
+def _in_lockstep(loader, device):
+    """The loader's batches until ANY rank has run out: a rank's shard may hold one sequence fewer,
+    or more samples the dataset gives up on, and every rank must take the same number of steps
+    (the gradient all-reduce pairs them). A plain pass-through on one rank."""
+    it = iter(loader)
+    while True:
+        batch = next(it, None)
+        if any_rank(batch is None, device):
+            return
+        yield batch
 
 
 def main(argv=None, variant="vit"):
@@ -119,7 +136,7 @@ def main(argv=None, variant="vit"):
 
     log(f"--- {tag} Training Configuration ---")
     log(f"Device: {device} x {world} rank(s)")
-    log(f"Training data: {'synthetic' if args.synthetic else TRAIN_DATA_DIR}")
+    log(f"Training data: {'synthetic' if args.synthetic else args.data_dir}")
     log(f"BEV Image Size for {tag}: {(H, W)}")
     log(f"Using Rotated IoU: {USE_ROTATED_IOU}")
     log(f"Batch Size: {args.batch}/GPU (global {args.batch * world}), Num Epochs: {args.epochs}, LR: {LEARNING_RATE}")
@@ -132,10 +149,16 @@ def main(argv=None, variant="vit"):
         loader = SyntheticBEVLoader(args.batch, args.batches_per_epoch, (H, W), rank=rank, device=device,
                                     resident=not args.fresh_batches, augment=args.augment)
     else:
-        if not Path(TRAIN_DATA_DIR).is_dir():
-            log(f"ERROR: Training data directory not found: {TRAIN_DATA_DIR} (use --synthetic)")
+        if not Path(args.data_dir).is_dir():
+            log(f"ERROR: Training data directory not found: {args.data_dir} (use --synthetic)")
             return 1
-        raise SystemExit("The Argoverse-2 dataset loader is outside this build's scope; use --synthetic")
+        if (H, W) != (GRID_HEIGHT_PX, GRID_WIDTH_PX):
+            raise SystemExit(f"--grid {args.grid}: Argoverse-2 rasters have the constants.py grid "
+                             f"{GRID_HEIGHT_PX}x{GRID_WIDTH_PX}; other grids need --synthetic")
+        from dataset import ArgoverseIntentNetDataset, FrameBatchLoader  # pandas / pyarrow only in this mode
+        train_set = ArgoverseIntentNetDataset(args.data_dir, num_sweeps=args.num_sweeps, is_train=True, device=device)
+        loader = FrameBatchLoader(train_set, args.batch, shuffle=True, rank=rank, world=world, augment=args.augment,
+                                  device=device)
 
     if USE_INTENTION_WEIGHTS and APPLY_INTENTION_DOWNSAMPLING:
         log("Warning: Both USE_INTENTION_WEIGHTS and APPLY_INTENTION_DOWNSAMPLING are True. "
@@ -163,7 +186,7 @@ def main(argv=None, variant="vit"):
         acc = torch.zeros(4, dtype=torch.float64, device=device)
         n_ok = 0
         t0 = time.perf_counter()
-        for batch_idx, batch in enumerate(loader):
+        for batch_idx, batch in enumerate(_in_lockstep(loader, device) if not args.synthetic else loader):
             d = trainer.step(batch)
             if d is None:
                 log(f"Warning: NaN detected at batch {batch_idx + 1}. Skipping batch.")

@@ -1,7 +1,8 @@
 """Box geometry of the reference's utils.py (anchors, axis/rotated IoU, decode, NMS, AP) and
 the LiDAR BEV voxelisation with its sweep ego transform (utils.py:27-33, 62-106; SURVEY.md §8f
-rank 1) and the BEV augmentations (utils.py:394-517; §8f rank 3) on the MI355X kernels. Map
-rasterisation (utils.py:108-225) belongs to the Argoverse-2 data pipeline, outside this build."""
+rank 1) and the BEV augmentations (utils.py:394-517; §8f rank 3) on the MI355X kernels, the
+HD-map rasterisation (utils.py:108-182) and the frame ground truth (utils.py:184-225) that
+dataset.py builds its samples from."""
 from __future__ import annotations
 
 import math
@@ -695,6 +696,59 @@ def rasterize_map_batch(items, H: int = GRID_HEIGHT_PX, W: int = GRID_WIDTH_PX, 
     lib.ivit_map_raster(ptr(t[0]), len(seg), ptr(t[1]), ptr(t[2]), ptr(t[3]), len(polys), ptr(t[4]), ptr(t[5]),
                         len(rows), max_edges, H, W, ptr(out), stream())
     return out
+
+
+def load_ego_poses(log_dir):
+    """utils.py:22-25: the log's city_SE3_egovehicle.feather as a DataFrame (pyarrow and pandas are
+    imported here, on use, so that importing this module needs neither)."""
+    import os
+    import pyarrow.feather as feather
+    return feather.read_feather(os.path.join(str(log_dir), "city_SE3_egovehicle.feather"))
+
+
+def quat_yaw(quat_xyzw: np.ndarray):
+    """-> (yaw [n] f64, valid [n] bool): the z angle of scipy's extrinsic as_euler('xyz') of the
+    normalised quaternions (away from gimbal lock), as ivit_intent_labels computes it; valid is
+    false where the norm is zero (scipy's from_quat raises ValueError there)."""
+    q = np.asarray(quat_xyzw, np.float64).reshape(-1, 4)
+    n = np.sqrt((q * q).sum(1))
+    valid = n > 0
+    x, y, z, w = (q / np.where(valid, n, 1.0)[:, None]).T
+    return np.where(valid, np.arctan2(2.0 * (w * z + x * y), 1.0 - 2.0 * (y * y + z * z)), 0.0), valid
+
+
+GT_COLUMNS = ("timestamp_ns", "category", "heuristic_intent", "tx_m", "ty_m", "width_m", "length_m",
+              "qx", "qy", "qz", "qw")
+
+
+def gt_columns(gt_df_with_intent, yaw=None) -> dict:
+    """The columns prepare_gt_for_frame reads, as numpy arrays (done once per log), with the
+    vehicle mask of utils.py:192-193 and the per-row yaw: the labelling kernel's when the log was
+    labelled in this process (``yaw``), else from the quaternion columns."""
+    from constants import VEHICLE_CATEGORIES
+    if "heuristic_intent" not in gt_df_with_intent:
+        raise KeyError("'heuristic_intent' column missing: run preprocess_intent_labels first")
+    c = {k: np.asarray(gt_df_with_intent[k]) for k in GT_COLUMNS}
+    quat = np.stack([c["qx"], c["qy"], c["qz"], c["qw"]], 1).astype(np.float64)
+    qyaw, c["quat_valid"] = quat_yaw(quat)
+    c["yaw"] = qyaw if yaw is None else np.asarray(yaw, np.float64)
+    c["gt_mask"] = np.isin(c["category"], sorted(VEHICLE_CATEGORIES)) & (c["heuristic_intent"] != -1)
+    return c
+
+
+def prepare_gt_for_frame(current_ts_ns: int, gt_df_with_intent, static_map=None) -> dict:
+    """utils.py:184-225: the frame's vehicle boxes [cx, cy, |w|, |l|, yaw] (f32) and intentions
+    (int64), in table order. Takes the annotation table (with ``heuristic_intent``) or the arrays
+    of gt_columns(); masks and gathers on arrays instead of the reference's per-row iterrows; rows
+    with a zero quaternion are dropped (the reference's ValueError branch, :213-216)."""
+    c = gt_df_with_intent if isinstance(gt_df_with_intent, dict) else gt_columns(gt_df_with_intent)
+    m = (c["timestamp_ns"] == current_ts_ns) & c["gt_mask"] & c["quat_valid"]
+    if not m.any():
+        return {'boxes_xywha': torch.empty((0, 5), dtype=torch.float32),
+                'intentions': torch.empty((0,), dtype=torch.long)}
+    boxes = np.stack([c["tx_m"][m], c["ty_m"][m], np.abs(c["width_m"][m]), np.abs(c["length_m"][m]), c["yaw"][m]], 1)
+    return {'boxes_xywha': torch.from_numpy(boxes.astype(np.float64)).to(torch.float32),
+            'intentions': torch.from_numpy(c["heuristic_intent"][m].astype(np.int64))}
 
 
 def rasterize_map_ego_centric(map_json_path, current_ego_pose, device=None) -> torch.Tensor:
