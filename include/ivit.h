@@ -404,6 +404,31 @@ int ivit_eval_post(const float* cls, const float* box_rel, const float* intent, 
                    long K, float conf_thr, double iou_thr, float* out_scores, float* out_boxes, long* out_intent,
                    long* out_count, void* work, long work_bytes, void* stream);
 
+/* Rotated NMS (the reference's future work, "refined evaluation (rotated NMS/IoU)"): the batched
+ * NMS and the eval post-processing above with the suppression test on the rotated boxes. Greedy
+ * NMS in torchvision's form with the IoU swapped: the order is the same stable descending sort of
+ * the scores (ties keep row order, -0 ties with +0); sorted positions are visited in order, an
+ * unsuppressed p is kept and suppresses every later q iff (double)rotated_iou(box[p], box[q]) > thr.
+ * rotated_iou is ivit_rotated_iou's function (f64 convex clip rounded to f32; area, intersection
+ * and union guards give 0) with the higher-ranked box as its FIRST argument (the clip's rounding
+ * is not symmetric): the decision for (p, q) equals ivit_rotated_iou(sorted, sorted)[p][q] > thr
+ * bit for bit. With thr < 0 every pair suppresses, disjoint ones included. Boxes with NaN / inf
+ * fields are decided by that same function, never by the kernel's f32 distance prefilter.
+ * Arguments, outputs (kept indices, counts, packed rows) and limits are those of
+ * ivit_nms_batched / ivit_eval_post; a single-sample call is n_samples = 1; samples with no rows
+ * get count 0. Workspace: the axis-aligned one (the eval form still reserves the worst-case mask,
+ * 8 * NA * ceil(NA / 64) bytes per sample) plus 112 bytes per row: 80 for the box's f64 corners
+ * and area, 32 for its f32 prefilter record. That is 152 B per row + 8 B per mask word for
+ * ivit_nms_rotated_batched and 188 B per row + the mask for ivit_eval_post_rotated.              */
+long ivit_nms_rotated_batched_workspace(long n_samples, long total, long mask_words);
+int ivit_nms_rotated_batched(const float* boxes_xywha, const float* scores, const long* seg, const long* mask_off,
+                             long n_samples, long total, long max_n, long mask_words, double iou_thr, long* keep,
+                             long* count, void* work, long work_bytes, void* stream);
+long ivit_eval_post_rotated_workspace(long B, long NA);
+int ivit_eval_post_rotated(const float* cls, const float* box_rel, const float* intent, const float* anchors, long B,
+                           long NA, long K, float conf_thr, double iou_thr, float* out_scores, float* out_boxes,
+                           long* out_intent, long* out_count, void* work, long work_bytes, void* stream);
+
 /* ---- BEV augmentation passes ----------------------------------------
  * Replaces the raster side of utils.augment_bev (utils.py:500-517): random_flip_bev's np.flip
  * (:399-401), random_rotate_bev's per-channel cv2.warpAffine (:425-438), random_scale_bev's

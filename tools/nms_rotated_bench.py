@@ -1,0 +1,226 @@
+"""Micro-benchmark of the rotated NMS (ivit_nms_rotated_batched / ivit_eval_post_rotated).
+
+* utils.postprocess_batch with rotated_nms False and True at B = 8 and B = 32, NA = 22 500
+  (the 400 x 720 grid, stride 8), on random-init style logits (every anchor passes the confidence
+  threshold: the worst case) and on a trained-like batch (about 2 % pass);
+* n = 4096 boxes: the only route to rotated NMS without the kernel, compute_rotated_iou n x n
+  + the matrix read back + the greedy walk on the host, against apply_nms(rotated=True); the two
+  keep lists are compared;
+* the share of lanes that have a pair in the exact phase of the mask kernel, computed from the
+  prefilter's definition (pairs per workgroup of 64 rows x 512 columns, 64 pairs per wave step),
+  not from hardware counters.
+Warm timings: every shape runs once before its timed window; a window ends in a device
+synchronise. Writes one JSON file (default profiles/nms_rotated_bench.json) and prints it."""
+import argparse
+import json
+import math
+import os
+import subprocess
+import sys
+import time
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+ROOT = os.path.join(HERE, "..")
+sys.path[:0] = [ROOT, os.path.join(ROOT, "visiontransformer-intention-prediction_amd")]
+import numpy as np
+import torch
+
+import utils
+
+CONF, THR = 0.1, 0.2
+
+
+def timed(fn, min_s=0.5, max_it=50):
+    """-> (ms per call, calls): one warm call, then calls until min_s has passed (at most max_it)."""
+    fn()
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    fn()
+    torch.cuda.synchronize()
+    one = time.perf_counter() - t0
+    it = int(max(2, min(max_it, math.ceil(min_s / max(one, 1e-6)))))
+    t0 = time.perf_counter()
+    for _ in range(it):
+        fn()
+    torch.cuda.synchronize()
+    return 1e3 * (time.perf_counter() - t0) / it, it
+
+
+def batch(B, NA, kind, seed):
+    g = torch.Generator().manual_seed(seed)
+    if kind == "random_init":  # sigmoid ~ 0.5 everywhere
+        cls = torch.randn(B, NA, generator=g) * 0.1
+    else:  # P(sigmoid(x) >= 0.1) = P(x >= ln(1/9)) = 2 % for x ~ N(-4.25, 1)
+        cls = torch.randn(B, NA, generator=g) - 4.25
+    box = torch.randn(B, NA, 6, generator=g) * 0.1
+    box[..., 4:] = torch.randn(B, NA, 2, generator=g)  # any yaw delta
+    it = torch.randn(B, NA, 8, generator=g)
+    return cls.cuda(), box.cuda(), it.cuda()
+
+
+def family(n, seed, side_per_sqrt_n=1.8):
+    rng = np.random.default_rng(seed)
+    b = np.empty((n, 5), np.float32)
+    b[:, 0:2] = rng.uniform(0.0, side_per_sqrt_n * math.sqrt(n), (n, 2))
+    b[:, 2] = rng.uniform(0.5, 2.5, n)
+    b[:, 3] = rng.uniform(1.0, 6.0, n)
+    b[:, 4] = rng.uniform(-math.pi, math.pi, n)
+    return torch.from_numpy(b).cuda(), torch.from_numpy(rng.uniform(0, 1, n).astype(np.float32)).cuda()
+
+
+def matrix_route(b, s, thr=THR):
+    """Rotated NMS without the kernel: sort, n x n device IoU, host greedy walk."""
+    order = torch.sort(s, descending=True, stable=True)[1]
+    sb = b[order]
+    iou = utils.compute_rotated_iou(sb, sb).cpu().numpy()
+    n = iou.shape[0]
+    sup = np.zeros(n, bool)
+    keep = []
+    for p in range(n):
+        if sup[p]:
+            continue
+        keep.append(p)
+        sup[p + 1:] |= iou[p, p + 1:].astype(np.float64) > thr
+    return order.cpu().numpy()[np.asarray(keep, np.int64)]
+
+
+def lane_share(sorted_boxes):
+    """Pairs surviving the f32 prefilter (centre distance, then separating axes), per workgroup (64 rows x 8 column blocks
+    of 64, upper triangle), and the share of lanes holding a pair when a workgroup works its
+    list 64 at a time (only its last step is partly filled)."""
+    n = sorted_boxes.shape[0]
+    npad = (n + 511) // 512 * 512
+    b = torch.zeros((npad, 5), device=sorted_boxes.device)
+    b[:n] = sorted_boxes
+    r = (torch.sqrt((b[:, 2].double() / 2) ** 2 + (b[:, 3].double() / 2) ** 2).float() * 1.0001)
+    valid = torch.arange(npad, device=b.device) < n
+    cs, sn = torch.cos(b[:, 4].double()).float(), torch.sin(b[:, 4].double()).float()
+    hw, hl = (b[:, 2] / 2).abs(), (b[:, 3] / 2).abs()
+
+    def upper(r0, r1):
+        return torch.arange(npad, device=b.device)[None, :] > torch.arange(r0, r1, device=b.device)[:, None]
+    pairs = steps = circle = 0
+    for r0 in range(0, npad, 2048):
+        rows = slice(r0, min(r0 + 2048, npad))
+        dx = b[rows, 0:1] - b[None, :, 0]
+        dy = b[rows, 1:2] - b[None, :, 1]
+        R = r[rows, None] + r[None, :]
+        cand = ~(dx * dx + dy * dy > R * R)
+        circle += int((cand & upper(r0, rows.stop) & valid[rows, None] & valid[None, :]).sum())
+        # the separating-axis stage (rot_sat_apart): a = row box, b = column box
+        ac, as_, aw, al = (v[rows, None] for v in (cs, sn, hw, hl))
+        bc, bs, bw, bl = (v[None, :] for v in (cs, sn, hw, hl))
+        C, S, sl = (ac * bc + as_ * bs).abs(), (as_ * bc - ac * bs).abs(), 1e-4 * R
+        apart = (dx * ac + dy * as_).abs() > aw + (bw * C + bl * S) + sl
+        apart |= (dy * ac - dx * as_).abs() > al + (bw * S + bl * C) + sl
+        apart |= (dx * bc + dy * bs).abs() > bw + (aw * C + al * S) + sl
+        apart |= (dy * bc - dx * bs).abs() > bl + (aw * S + al * C) + sl
+        cand &= ~apart
+        cand &= upper(r0, rows.stop) & valid[rows, None] & valid[None, :]
+        cnt = cand.reshape(-1, 64, npad // 512, 512).sum((1, 3))
+        pairs += int(cnt.sum())
+        steps += int(((cnt + 63) // 64).sum())
+    return {"pairs": pairs, "pairs_per_box": round(pairs / max(n, 1), 2),
+            "pairs_per_box_after_circle_test": round(circle / max(n, 1), 2),
+            "exact_phase_lane_share": round(pairs / max(64 * steps, 1), 4)}
+
+
+def eval_loop_ms(B, rotated, steps=8, warmup=3):
+    """bench.py's eval loop (config 4: bf16 IntentNetViT forward at 400 x 720 with random-init
+    weights, every anchor passing; utils.PostPipeline runs batch k's post-processing beside batch
+    k+1's forward) -> ms per step."""
+    import model_vit
+    from synthetic import synthetic_batch
+    torch.manual_seed(0)
+    model = model_vit.IntentNetViT(backbone_cfg={"img_size": (400, 720)}).cuda().set_compute_dtype(torch.bfloat16)
+    model.train(False)
+    anchors = utils.generate_anchors(400, 720, 8)
+    batch = synthetic_batch(B, (400, 720), torch.Generator().manual_seed(1234), device=torch.device("cuda"))
+    pipe = utils.PostPipeline(anchors, CONF, THR, rotated_nms=rotated)
+    kept = []
+
+    def step():
+        with torch.inference_mode():
+            prev = pipe.push(*model(batch["lidar_bev"], batch["map_bev"]))
+            if prev is not None:
+                kept.append(sum(int(p["pred_scores"].numel()) for p in prev))
+    for _ in range(warmup):
+        step()
+    pipe.flush()
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    for _ in range(steps):
+        step()
+    pipe.flush()
+    torch.cuda.synchronize()
+    return 1e3 * (time.perf_counter() - t0) / steps, kept[-1] / B
+
+
+def main():
+    ap = argparse.ArgumentParser(description=__doc__.splitlines()[0])
+    ap.add_argument("--no-eval-loop", action="store_true", help="skip the forward + PostPipeline loop at B = 32")
+    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "nms_rotated_bench.json"))
+    ap.add_argument("--commit", default=None, help="commit hash to record (default: git rev-parse HEAD)")
+    ap.add_argument("--batches", type=int, nargs="*", default=[8, 32])
+    args = ap.parse_args()
+    if not torch.cuda.is_available():
+        raise SystemExit("nms_rotated_bench.py needs a ROCm GPU")
+    commit = args.commit
+    if commit is None:
+        r = subprocess.run(["git", "-C", ROOT, "rev-parse", "HEAD"], capture_output=True, text=True)
+        commit = r.stdout.strip() if r.returncode == 0 else "unknown"
+    out = {"commit": commit, "device": torch.cuda.get_device_name(0), "conf_thr": CONF, "iou_thr": THR,
+           "postprocess_batch": [], "n4096": {}}
+    anchors = utils.generate_anchors(400, 720, 8)
+    NA = anchors.shape[0]
+    for kind in ("random_init", "trained_like"):
+        for B in args.batches:
+            cls, box, it = batch(B, NA, kind, 17)
+            row = {"kind": kind, "B": B, "NA": NA}
+            for rot in (False, True):
+                fn = lambda: utils.postprocess_batch(cls, box, it, anchors, CONF, THR, rotated_nms=rot)  # noqa: E731
+                ms, calls = timed(fn)
+                res = fn()
+                tag = "rotated" if rot else "axis"
+                row[f"{tag}_ms"] = round(ms, 3)
+                row[f"{tag}_calls"] = calls
+                row[f"{tag}_kept_per_sample"] = round(sum(p["pred_scores"].numel() for p in res) / B, 1)
+            s0 = torch.sigmoid(cls[0])
+            idx = torch.where(s0 >= CONF)[0]
+            row["passing_per_sample"] = int(idx.numel())
+            dec = utils.decode_box_predictions(box[0][idx], anchors[idx])
+            row["sample0"] = lane_share(dec[torch.sort(s0[idx], descending=True, stable=True)[1]])
+            row["rotated_over_axis"] = round(row["rotated_ms"] / row["axis_ms"], 2)
+            out["postprocess_batch"].append(row)
+            print(json.dumps(row), flush=True)
+    n = 4096
+    b, s = family(n, 3)
+    m_ms, m_calls = timed(lambda: matrix_route(b, s), min_s=0.5, max_it=5)
+    k_ms, k_calls = timed(lambda: utils.apply_nms(b, s, THR, rotated=True))
+    a_ms, _ = timed(lambda: utils.apply_nms(b, s, THR))
+    want, got = matrix_route(b, s), utils.apply_nms(b, s, THR, rotated=True).cpu().numpy()
+    out["n4096"] = {"n": n, "matrix_route_ms": round(m_ms, 3), "matrix_route_calls": m_calls,
+                    "apply_nms_rotated_ms": round(k_ms, 3), "apply_nms_rotated_calls": k_calls,
+                    "apply_nms_axis_ms": round(a_ms, 3), "speedup_over_matrix_route": round(m_ms / k_ms, 1),
+                    "keeps_equal": bool(np.array_equal(want, got)), "kept": int(got.shape[0]),
+                    **lane_share(b[torch.sort(s, descending=True, stable=True)[1]])}
+    if not args.no_eval_loop:
+        # alternating, axis first and last: the spread between the two axis runs is the noise
+        loop = {}
+        for tag, rot in (("axis", False), ("rotated", True), ("axis_again", False)):
+            ms, kept = eval_loop_ms(32, rot)
+            loop[f"{tag}_ms_per_step"] = round(ms, 3)
+            loop[f"{tag}_kept_per_sample"] = round(kept, 1)
+        out["eval_loop_B32"] = loop
+        print(json.dumps(loop), flush=True)
+    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+    with open(args.out, "w") as f:
+        json.dump(out, f, indent=1)
+        f.write("\n")
+    print(json.dumps(out["n4096"]))
+    if not out["n4096"]["keeps_equal"] or not k_ms < m_ms:
+        raise SystemExit("rotated NMS kernel: keep lists differ from the matrix route, or it is not faster")
+
+
+if __name__ == "__main__":
+    main()

@@ -59,3 +59,4 @@ VEHICLE_CATEGORIES = {"REGULAR_VEHICLE", "LARGE_VEHICLE", "BUS", "BOX_TRUCK", "T
 DETECTION_IOU_THRESHOLDS = [0.5, 0.6, 0.7, 0.8, 0.9]
 IOU_THRESHOLD_FOR_INTENTION_MATCH = 0.5
 EVAL_USE_ROTATED_IOU = False
+EVAL_USE_ROTATED_NMS = False  # eval_vit.py --rotated-nms: suppress on the rotated IoU of the decoded boxes

@@ -89,20 +89,32 @@ IVIT_DEV void clip_poly(Poly& P, const Poly& Q) {
   }
 }
 
-IVIT_DEV float rotated_iou(const float* a, const float* b) {
-  Poly pa, pb;
-  rect_poly(a, pa);
-  rect_poly(b, pb);
-  const double A1 = fabs(poly_area_signed(pa)), A2 = fabs(poly_area_signed(pb));
+// A box prepared once for many pair tests: rect_poly's corners put in ccw order, and the area taken
+// BEFORE the reordering (the shoelace sum of the reversed polygon rounds differently).
+IVIT_DEV double rect_prepare(const float* b, Poly& p) {
+  rect_poly(b, p);
+  const double A = fabs(poly_area_signed(p));
+  make_ccw(p);
+  return A;
+}
+
+// IoU of two prepared boxes (rect_prepare): pa is clipped by pb, so the argument order is part of
+// the result's last bits. Area / intersection / union guards return 0.
+IVIT_DEV float rotated_iou(const Poly& pa, double A1, const Poly& pb, double A2) {
   if (A1 < 1e-6 || A2 < 1e-6) return 0.f;
-  make_ccw(pa);
-  make_ccw(pb);
-  clip_poly(pa, pb);
-  const double inter = pa.n >= 3 ? fabs(poly_area_signed(pa)) : 0.0;
+  Poly pc = pa;
+  clip_poly(pc, pb);
+  const double inter = pc.n >= 3 ? fabs(poly_area_signed(pc)) : 0.0;
   if (!(inter > 1e-7)) return 0.f;
   const double u = A1 + A2 - inter;
   if (!(u > 1e-6)) return 0.f;
   return (float)(inter / u);
+}
+
+IVIT_DEV float rotated_iou(const float* a, const float* b) {
+  Poly pa, pb;
+  const double A1 = rect_prepare(a, pa), A2 = rect_prepare(b, pb);
+  return rotated_iou(pa, A1, pb, A2);
 }
 
 }  // namespace ivit

@@ -551,6 +551,202 @@ __global__ __launch_bounds__(256) void nms_scan_b_kernel(const unsigned long lon
   nms_scan_body(mask_all + sv.mo(sm), n, (int)((n + 63) / 64), order_all + o, keep_all + o, count + sm);
 }
 
+// ---- rotated NMS: the same sort, mask layout, walk and gather; only the stage that fills the
+// mask differs. Sorted box p suppresses a later sorted box q iff
+// (double)rotated_iou(box[p], box[q]) > thr, the higher-ranked box first (geom.h: the clip is not
+// symmetric in its rounding), i.e. the decision equals ivit_rotated_iou(sorted, sorted)[p][q] > thr.
+//
+// Per sorted box, once (nms_rot_prep_kernel): the ccw f64 corners and the area that
+// rotated_iou(Poly, A, Poly, A) takes (10 doubles: x[4], y[4], area, pad) and an f32 prefilter
+// record (cx, cy, r, -; cos yaw, sin yaw, |w/2|, |l/2|): r is the half diagonal
+// sqrt((w/2)^2 + (l/2)^2), rounded from f64 and inflated by NMS_ROT_SLACK. Every corner lies within the true half diagonal of the centre, so two boxes
+// whose centres are further apart than r_p + r_q are disjoint. The f32 test d2 > (r_p + r_q)^2 has
+// a relative rounding error below 2^-21 in d2 (one rounding in each difference, square, and the
+// sum) and below 2^-22 in the right side; the slack of 1e-4 per radius exceeds both by two orders
+// of magnitude and leaves a true gap of >= 9.9e-5 (r_p + r_q) between the rejected boxes. A box
+// that passes the area guard (>= 1e-6) has r >= 7e-4, so the gap is >= 1.4e-7, while the f64 edge
+// tests of the clip carry an error of ~1e-16 x (coordinate magnitude <= 1e6) = ~2e-10 of the same
+// units: the clip of a rejected pair is empty and its IoU is exactly 0. Pairs that pass the circle
+// test take the separating-axis test of the two rectangles in f32 (rot_sat_apart: the four edge
+// normals; two rectangles are disjoint iff one of them separates them): with |d| <= r_p + r_q
+// its projections carry an absolute rounding error below 1e-6 (r_p + r_q) (the cosines and sines
+// are rounded from f64), and a pair is rejected only if an axis separates it by more than
+// 1e-4 (r_p + r_q): the same true gap, the same argument (whichever box owns the axis: the
+// clipped polygon's vertices stay that far outside one edge line of the clipping rectangle's
+// half strip). On an eval sample in which every anchor passes it halves the exact tests
+// (91 -> 46 per box). Boxes outside that range (|cx|, |cy| or r above 1e6) or with a non-finite
+// field get r = NaN: every comparison with it is false and the pair falls through to the exact
+// test. With thr < 0 (or NaN) the prefilter is off: an IoU of 0 exceeds a negative threshold.
+constexpr float NMS_ROT_SLACK = 1.0001f;
+constexpr float NMS_ROT_RANGE = 1e6f;
+
+// grid (ceil(max n / 256), samples). boxes: the unsorted xywha rows of every sample; order: each
+// sample's stable descending score order (local row indices).
+__global__ __launch_bounds__(256) void nms_rot_prep_kernel(const float* __restrict__ boxes,
+                                                           const int* __restrict__ order, SegView sv,
+                                                           double* __restrict__ rp, float4* __restrict__ rc) {
+  const int sm = blockIdx.y;
+  const long o = sv.lo(sm), n = sv.n(sm);
+  const long p = (long)blockIdx.x * 256 + threadIdx.x;
+  if (p >= n) return;
+  const float* b = boxes + (o + order[o + p]) * 5;
+  Poly P;
+  const double A = rect_prepare(b, P);
+  double* d = rp + (o + p) * 10;
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    d[i] = P.x[i];
+    d[4 + i] = P.y[i];
+  }
+  d[8] = A;
+  d[9] = 0.0;
+  const double hw = (double)b[2] / 2.0, hl = (double)b[3] / 2.0;
+  const float r = (float)sqrt(hw * hw + hl * hl) * NMS_ROT_SLACK;
+  // written so that a NaN in any field fails it
+  const bool sane = fabsf(b[0]) <= NMS_ROT_RANGE && fabsf(b[1]) <= NMS_ROT_RANGE && r <= NMS_ROT_RANGE &&
+                    fabsf(b[4]) < INFINITY;
+  rc[2 * (o + p)] = make_float4(b[0], b[1], sane ? r : __builtin_nanf(""), 0.f);
+  rc[2 * (o + p) + 1] = make_float4((float)cos((double)b[4]), (float)sin((double)b[4]), fabsf(b[2] / 2.f),
+                                    fabsf(b[3] / 2.f));
+}
+
+// a, b: (cos, sin, half width, half length) of two boxes whose centres differ by (dx, dy). True iff
+// an edge normal of either separates them by more than slack. u = (cos, sin) is a box's width
+// axis, v = (-sin, cos) its length axis; u_a.u_b = v_a.v_b = cos(ya - yb), u_a.v_b = -v_a.u_b =
+// sin(ya - yb). A NaN anywhere makes every comparison false.
+IVIT_DEV bool rot_sat_apart(float dx, float dy, float4 a, float4 b, float slack) {
+  const float C = fabsf(a.x * b.x + a.y * b.y), S = fabsf(a.y * b.x - a.x * b.y);
+  if (fabsf(dx * a.x + dy * a.y) > a.z + (b.z * C + b.w * S) + slack) return true;
+  if (fabsf(dy * a.x - dx * a.y) > a.w + (b.z * S + b.w * C) + slack) return true;
+  if (fabsf(dx * b.x + dy * b.y) > b.z + (a.z * C + a.w * S) + slack) return true;
+  if (fabsf(dy * b.x - dx * b.y) > b.w + (a.z * S + a.w * C) + slack) return true;
+  return false;
+}
+
+// One 64-thread workgroup per (row block rb, chunk of NMS_CB column blocks >= rb), as
+// nms_mask_body. Almost every pair is disjoint and the exact clip is a few thousand f64
+// operations, so a lane-per-row loop over the columns would run the clip on the few lanes whose
+// pair overlaps while the rest of the wave waits. Instead the chunk is worked in passes of
+// NMS_ROT_KC columns:
+//   1. lane = row: the f32 prefilter against each of the pass's columns (their records in LDS);
+//      the surviving (column block, row, column) triples are appended to an LDS list in ballot
+//      order (the wave's count is uniform, no atomics);
+//   2. lane = list entry: while the list holds 64 entries, 64 of them are taken from its front,
+//      one exact rotated_iou per lane; a suppressing pair sets its bit in the (column block, row)
+//      LDS word (atomicOr). What is left (< 64) stays in the list for the next pass, also across
+//      column blocks, and only the chunk's last step runs with idle lanes;
+//   3. lane = row, at the end of the chunk: the NMS_CB words go to the mask.
+// A list per 64 x 32 columns that was emptied after every pass ran the exact phase with 26 % of
+// its lanes holding a pair on an eval sample in which all 22 500 anchors pass (11-20 % on sparse
+// samples): a pass seldom yields 64 pairs.
+// LDS: list (64 left over + 64 x NMS_ROT_KC new entries of 15 bits) 1152 B + records 2 KiB +
+// words 4 KiB = 7296 B per one-wave workgroup: 22 fit in a CU's 160 KiB, more than the 20 the
+// kernel's 88 VGPRs allow (5 waves per SIMD), so LDS does not lower the occupancy. NMS_ROT_KC = 32
+// would cap it at 4 waves per SIMD. The clip's polygons are indexed at run time and live in scratch, so the exact
+// phase is latency-bound and wants the waves.
+constexpr int NMS_ROT_KC = 8;
+IVIT_DEV void nms_rot_mask_body(const double* __restrict__ rp, const float4* __restrict__ rc, long n, int nw,
+                                double thr, int pre, unsigned long long* __restrict__ mask, int rb, int cb0) {
+  __shared__ float4 ccol[64], ccol2[64];
+  __shared__ unsigned short plist[64 + 64 * NMS_ROT_KC];
+  __shared__ unsigned long long bits_s[NMS_CB][64];
+  const int t = threadIdx.x;
+  const long i = (long)rb * 64 + t;
+  const bool row_ok = i < n;
+  const float4 me = row_ok ? rc[2 * i] : make_float4(0.f, 0.f, 0.f, 0.f);
+  const float4 me2 = row_ok ? rc[2 * i + 1] : make_float4(0.f, 0.f, 0.f, 0.f);
+  const unsigned long long below = t ? (~0ull >> (64 - t)) : 0ull;  // the lanes before this one
+  const int cbs = max(cb0, rb), cb1 = min(cb0 + NMS_CB, nw);
+#pragma unroll
+  for (int c = 0; c < NMS_CB; ++c) bits_s[c][t] = 0ull;
+  // one exact test: list entry = (column block - cb0) << 12 | row << 6 | column
+  auto exact = [&](int ent) {
+    const int ci = ent >> 12, r = (ent >> 6) & 63, k = ent & 63;
+    const double* a = rp + ((long)rb * 64 + r) * 10;
+    const double* b = rp + ((long)(cb0 + ci) * 64 + k) * 10;
+    Poly pa, pb;
+    pa.n = 4;
+    pb.n = 4;
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+      pa.x[q] = a[q];
+      pa.y[q] = a[4 + q];
+      pb.x[q] = b[q];
+      pb.y[q] = b[4 + q];
+    }
+    if ((double)rotated_iou(pa, a[8], pb, b[8]) > thr) atomicOr(&bits_s[ci][r], 1ull << k);
+  };
+  int cnt = 0;  // list length, wave-uniform, < 64 between passes
+  for (int cb = cbs; cb < cb1; ++cb) {
+    const long cj = (long)cb * 64 + t;
+    __syncthreads();  // the previous block's records are no longer read
+    if (cj < n) {
+      ccol[t] = rc[2 * cj];
+      ccol2[t] = rc[2 * cj + 1];
+    }
+    __syncthreads();
+    const int lim = (int)min((long)64, n - (long)cb * 64);
+    // the diagonal block tests (and keeps) only the boxes after this one
+    const int kfirst = cb == rb ? t + 1 : 0;
+    const int tag = ((cb - cb0) << 12) | (t << 6);
+    for (int kc = 0; kc < lim; kc += NMS_ROT_KC) {
+      const int k1 = min(kc + NMS_ROT_KC, lim);
+      for (int k = kc; k < k1; ++k) {
+        bool cand = row_ok && k >= kfirst;
+        if (cand && pre) {
+          const float4 c = ccol[k];
+          const float dx = me.x - c.x, dy = me.y - c.y, R = me.z + c.z;
+          // a NaN on either side: both tests are false, the pair stays
+          if (dx * dx + dy * dy > R * R || rot_sat_apart(dx, dy, me2, ccol2[k], 1e-4f * R)) cand = false;
+        }
+        const unsigned long long bal = __ballot(cand);
+        if (cand) plist[cnt + __popcll(bal & below)] = (unsigned short)(tag | k);
+        cnt += __popcll(bal);
+      }
+      if (cnt < 64) continue;  // wave-uniform
+      __syncthreads();
+      const int full = cnt & ~63, rem = cnt - full;
+      for (int e0 = 0; e0 < full; e0 += 64) exact(plist[e0 + t]);
+      const int left = t < rem ? plist[full + t] : 0;
+      __syncthreads();  // every entry has been read: the rest moves to the front
+      if (t < rem) plist[t] = (unsigned short)left;
+      cnt = rem;
+    }
+  }
+  __syncthreads();
+  if (t < cnt) exact(plist[t]);
+  __syncthreads();
+  for (int cb = cbs; cb < cb1; ++cb) {
+    const unsigned long long keep_mask = cb == rb ? (t == 63 ? 0ull : ~0ull << (t + 1)) : ~0ull;
+    if (row_ok) mask[i * nw + cb] = bits_s[cb - cb0][t] & keep_mask;
+  }
+}
+
+// grid (ceil(nwmax / NMS_CB), nwmax, samples)
+__global__ __launch_bounds__(64) void nms_rot_mask_b_kernel(const double* __restrict__ rp_all,
+                                                            const float4* __restrict__ rc_all, SegView sv, double thr,
+                                                            int pre, unsigned long long* __restrict__ mask_all) {
+  const int sm = blockIdx.z;
+  const long o = sv.lo(sm), n = sv.n(sm);
+  const int nw = (int)((n + 63) / 64);
+  const int cb0 = blockIdx.x * NMS_CB, rb = blockIdx.y;
+  if (cb0 >= nw || rb >= nw || cb0 + NMS_CB <= rb) return;
+  nms_rot_mask_body(rp_all + o * 10, rc_all + 2 * o, n, nw, thr, pre, mask_all + sv.mo(sm), rb, cb0);
+}
+
+// nms_scan_body loads rows 0 and 1 before it looks at n: an empty sample is settled here
+__global__ __launch_bounds__(256) void nms_rot_scan_b_kernel(const unsigned long long* __restrict__ mask_all,
+                                                             SegView sv, const int* __restrict__ order_all,
+                                                             long* __restrict__ keep_all, long* __restrict__ count) {
+  const int sm = blockIdx.x;
+  const long o = sv.lo(sm), n = sv.n(sm);
+  if (n <= 0) {
+    if (threadIdx.x == 0) count[sm] = 0;
+    return;
+  }
+  nms_scan_body(mask_all + sv.mo(sm), n, (int)((n + 63) / 64), order_all + o, keep_all + o, count + sm);
+}
+
 // ---- eval post-processing (eval_vit.py:156-176) for a whole batch, capacity NA rows per sample.
 struct PostWs {
   int* n;            // [S] rows passing the confidence threshold
@@ -776,6 +972,60 @@ extern "C" int ivit_nms_batched(const float* boxes_xywha, const float* scores, c
   return 0;
 }
 
+// Rotated form of ivit_nms_batched: the axis workspace (the sort stage is shared and still writes
+// its corner rows) plus the per-box polygons (80 B per row) and prefilter records (32 B per row).
+extern "C" long ivit_nms_rotated_batched_workspace(long n_samples, long total, long mask_words) {
+  if (n_samples <= 0 || total <= 0) return 64;
+  return ivit_nms_batched_workspace(n_samples, total, mask_words) + al16(80 * total) + al16(32 * total);
+}
+
+extern "C" int ivit_nms_rotated_batched(const float* boxes_xywha, const float* scores, const long* seg,
+                                        const long* mask_off, long n_samples, long total, long max_n, long mask_words,
+                                        double iou_thr, long* keep, long* count, void* work, long work_bytes,
+                                        void* stream) {
+  IVIT_CHECK_ARG(max_n <= 64L * NMS_MAXW, "ivit_nms_rotated_batched: n=%ld exceeds %d", max_n, 64 * NMS_MAXW);
+  IVIT_CHECK_ARG(n_samples < 65536 && total < (1L << 31),
+                 "ivit_nms_rotated_batched: too many samples / rows (%ld, %ld)", n_samples, total);
+  IVIT_CHECK_ARG(work_bytes >= ivit_nms_rotated_batched_workspace(n_samples, total, mask_words),
+                 "ivit_nms_rotated_batched: workspace too small");
+  hipStream_t st = ivit_stream(stream);
+  if (n_samples <= 0) return 0;
+  if (max_n <= 0 || total <= 0) {
+    (void)hipMemsetAsync(count, 0, sizeof(long) * n_samples, st);
+    IVIT_LAUNCH_CHECK();
+    return 0;
+  }
+  const int nwmax = (int)((max_n + 63) / 64);
+  char* w = (char*)(((uintptr_t)work + 15) & ~(uintptr_t)15);
+  int* order = (int*)w;
+  w += al16(4 * total);
+  float* sb = (float*)w;
+  w += al16(20 * total);
+  unsigned long long* mask = (unsigned long long*)w;
+  w += al16(8 * mask_words);
+  unsigned* k0 = (unsigned*)w;
+  w += al16(4 * total);
+  unsigned* k1 = (unsigned*)w;
+  w += al16(4 * total);
+  int* v0 = (int*)w;
+  w += al16(4 * total);
+  int* v1 = (int*)w;
+  w += al16(4 * total);
+  double* rp = (double*)w;
+  w += al16(80 * total);
+  float4* rc = (float4*)w;
+  const SegView sv{seg, mask_off, nullptr, 0, 0};
+  hipLaunchKernelGGL(nms_sort_b_kernel, dim3(n_samples), dim3(PS_T), 0, st, boxes_xywha, scores, seg, k0, v0, k1, v1,
+                     order, sb);
+  hipLaunchKernelGGL(nms_rot_prep_kernel, dim3(ivit_cdiv(max_n, 256), n_samples), dim3(256), 0, st, boxes_xywha, order,
+                     sv, rp, rc);
+  hipLaunchKernelGGL(nms_rot_mask_b_kernel, dim3(ivit_cdiv(nwmax, NMS_CB), nwmax, n_samples), dim3(64), 0, st, rp, rc,
+                     sv, iou_thr, iou_thr >= 0.0 ? 1 : 0, mask);
+  hipLaunchKernelGGL(nms_rot_scan_b_kernel, dim3(n_samples), dim3(256), 0, st, mask, sv, order, keep, count);
+  IVIT_LAUNCH_CHECK();
+  return 0;
+}
+
 // Eval post-processing for a batch (eval_vit.py:156-176): four launches, no host round trip.
 namespace {
 struct PostLayout {
@@ -835,6 +1085,59 @@ extern "C" int ivit_eval_post(const float* cls, const float* box_rel, const floa
   hipLaunchKernelGGL(nms_mask_b_kernel, dim3(ivit_cdiv(nw, NMS_CB), nw, B), dim3(64), 0, st, w.sb, sv,
                      nms_thr(iou_thr), w.mask);
   hipLaunchKernelGGL(nms_scan_b_kernel, dim3(B), dim3(256), 0, st, w.mask, sv, w.order, w.keep, out_count);
+  hipLaunchKernelGGL(post_gather_kernel, dim3(ivit_cdiv(NA, 256), B), dim3(256), 0, st, out_count, intent, (int)NA,
+                     (int)K, w, out_scores, out_boxes, out_intent);
+  IVIT_LAUNCH_CHECK();
+  return 0;
+}
+
+// ivit_eval_post with the rotated suppression test: five launches (the per-box polygons are one
+// more), the same outputs. The workspace is the axis one plus 112 B per row.
+extern "C" long ivit_eval_post_rotated_workspace(long B, long NA) {
+  if (B <= 0 || NA <= 0) return 64;
+  return post_layout(B, NA).bytes + al16(80 * B * NA) + al16(32 * B * NA);
+}
+
+extern "C" int ivit_eval_post_rotated(const float* cls, const float* box_rel, const float* intent, const float* anchors,
+                                      long B, long NA, long K, float conf_thr, double iou_thr, float* out_scores,
+                                      float* out_boxes, long* out_intent, long* out_count, void* work, long work_bytes,
+                                      void* stream) {
+  IVIT_CHECK_ARG(B >= 0 && B < 65536 && NA >= 0 && K >= 1, "ivit_eval_post_rotated: bad sizes (B %ld, NA %ld, K %ld)",
+                 B, NA, K);
+  IVIT_CHECK_ARG(NA <= 64L * NMS_MAXW, "ivit_eval_post_rotated: NA=%ld exceeds %d", NA, 64 * NMS_MAXW);
+  IVIT_CHECK_ARG(work_bytes >= ivit_eval_post_rotated_workspace(B, NA), "ivit_eval_post_rotated: workspace too small");
+  hipStream_t st = ivit_stream(stream);
+  if (B == 0) return 0;
+  if (NA == 0) {
+    (void)hipMemsetAsync(out_count, 0, sizeof(long) * B, st);
+    IVIT_LAUNCH_CHECK();
+    return 0;
+  }
+  const PostLayout L = post_layout(B, NA);
+  char* base = (char*)(((uintptr_t)work + 15) & ~(uintptr_t)15);
+  PostWs w;
+  w.n = (int*)(base + L.off[0]);
+  w.anchor = (int*)(base + L.off[1]);
+  w.score = (float*)(base + L.off[2]);
+  w.box = (float*)(base + L.off[3]);
+  w.k0 = (unsigned*)(base + L.off[4]);
+  w.k1 = (unsigned*)(base + L.off[5]);
+  w.v0 = (int*)(base + L.off[6]);
+  w.v1 = (int*)(base + L.off[7]);
+  w.order = (int*)(base + L.off[8]);
+  w.sb = (float*)(base + L.off[9]);
+  w.keep = (long*)(base + L.off[10]);
+  w.mask = (unsigned long long*)(base + L.off[11]);
+  const long tail = L.off[11] + al16(8 * B * NA * ((NA + 63) / 64));
+  double* rp = (double*)(base + tail);
+  float4* rc = (float4*)(base + tail + al16(80 * B * NA));
+  const int nw = (int)((NA + 63) / 64);
+  const SegView sv{nullptr, nullptr, w.n, NA, NA * nw};
+  hipLaunchKernelGGL(post_select_kernel, dim3(B), dim3(PS_T), 0, st, cls, box_rel, anchors, (int)NA, conf_thr, w);
+  hipLaunchKernelGGL(nms_rot_prep_kernel, dim3(ivit_cdiv(NA, 256), B), dim3(256), 0, st, w.box, w.order, sv, rp, rc);
+  hipLaunchKernelGGL(nms_rot_mask_b_kernel, dim3(ivit_cdiv(nw, NMS_CB), nw, B), dim3(64), 0, st, rp, rc, sv, iou_thr,
+                     iou_thr >= 0.0 ? 1 : 0, w.mask);
+  hipLaunchKernelGGL(nms_rot_scan_b_kernel, dim3(B), dim3(256), 0, st, w.mask, sv, w.order, w.keep, out_count);
   hipLaunchKernelGGL(post_gather_kernel, dim3(ivit_cdiv(NA, 256), B), dim3(256), 0, st, out_count, intent, (int)NA,
                      (int)K, w, out_scores, out_boxes, out_intent);
   IVIT_LAUNCH_CHECK();

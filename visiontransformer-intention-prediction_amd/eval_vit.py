@@ -13,7 +13,8 @@ built on the GPU, on the constants.py grid only; ``--synthetic`` evaluates seede
 pickled ``BasicBlock`` class in ``backbone_cfg`` is allow-listed by name); post-processing runs
 on the device for the whole batch (utils.postprocess_batch, pipelined by utils.PostPipeline); the mAP / intention matching
 walk runs on the device for all samples in one launch (metrics.match_device, ivit_det_match). The reference's undefined names (eval_vit.py:12-13,39,196,219)
-come from constants.py / utils.py.
+come from constants.py / utils.py. ``--rotated-nms`` (off by default; the reference's future work)
+makes the NMS suppress on the rotated IoU of the decoded boxes instead of their axis-aligned corners.
 """
 from __future__ import annotations
 
@@ -24,10 +25,9 @@ from pathlib import Path
 import torch
 
 import model_vit
-from constants import (ANCHOR_CONFIGS_PAPER, DETECTION_IOU_THRESHOLDS, EVAL_USE_ROTATED_IOU, GRID_HEIGHT_PX,
-                       GRID_WIDTH_PX, INTENTIONS_MAP_REV, IOU_THRESHOLD_FOR_INTENTION_MATCH, LIDAR_SWEEPS,
-                       LIDAR_TOTAL_CHANNELS,
-                       MAP_CHANNELS, NUM_INTENTION_CLASSES)
+from constants import (ANCHOR_CONFIGS_PAPER, DETECTION_IOU_THRESHOLDS, EVAL_USE_ROTATED_IOU, EVAL_USE_ROTATED_NMS,
+                       GRID_HEIGHT_PX, GRID_WIDTH_PX, INTENTIONS_MAP_REV, IOU_THRESHOLD_FOR_INTENTION_MATCH,
+                       LIDAR_SWEEPS, LIDAR_TOTAL_CHANNELS, MAP_CHANNELS, NUM_INTENTION_CLASSES)
 from metrics import detection_map_device as detection_map, intention_matches_device as intention_matches
 from model_vit import IntentNetViT
 from synthetic import SyntheticBEVLoader
@@ -78,15 +78,18 @@ def parse_args(argv=None):
     ap.add_argument("--dtype", choices=["bf16", "fp32"], default="fp32")
     ap.add_argument("--rotated", action="store_true", default=EVAL_USE_ROTATED_IOU,
                     help="rotated IoU for mAP / matching (device kernel; no shapely needed)")
+    ap.add_argument("--rotated-nms", action="store_true", default=EVAL_USE_ROTATED_NMS,
+                    help="suppress on the rotated IoU of the decoded boxes (independent of --rotated)")
     return ap.parse_args(argv)
 
 
-def run_inference(model, loader, anchors, conf=CONFIDENCE_THRESHOLD, nms=NMS_IOU_THRESHOLD):
+def run_inference(model, loader, anchors, conf=CONFIDENCE_THRESHOLD, nms=NMS_IOU_THRESHOLD, rotated_nms=False):
     """eval_vit.py:136-180: forward + post-processing per batch, in loader order. The
     post-processing of a batch (utils.PostPipeline) runs beside the next batch's forward; results
-    are the per-batch postprocess_batch ones, appended in the same order."""
+    are the per-batch postprocess_batch ones, appended in the same order. ``rotated_nms``: the
+    NMS suppresses on the rotated IoU (utils.apply_nms(rotated=True))."""
     results = []
-    pipe = PostPipeline(anchors, conf, nms)
+    pipe = PostPipeline(anchors, conf, nms, rotated_nms=rotated_nms)
     gts = []
 
     def emit(preds):
@@ -123,6 +126,7 @@ def main_eval_vit(argv=None, variant="vit"):
     print(f"--- {tag} Model Evaluation ---")
     print(f"Torch version: {torch.__version__}, device: {torch.cuda.get_device_name(0)}")
     print(f"Evaluation using Rotated IoU for mAP/matching: {args.rotated}")
+    print(f"Evaluation using Rotated NMS: {args.rotated_nms}")
 
     ckpt = None
     if Path(args.checkpoint).is_file():
@@ -176,7 +180,7 @@ def main_eval_vit(argv=None, variant="vit"):
     print(f"Anchors for {tag} evaluation generated (stride {stride}), shape: {tuple(anchors.shape)}")
 
     t0 = time.perf_counter()
-    results = run_inference(model, loader, anchors)
+    results = run_inference(model, loader, anchors, rotated_nms=args.rotated_nms)
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
     print(f"Collected results for {len(results)} samples ({len(results) / dt:.2f} samples/s incl. host transfer)")

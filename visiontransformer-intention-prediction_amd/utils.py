@@ -86,18 +86,24 @@ def nms_device(boxes_xywha: torch.Tensor, scores: torch.Tensor, iou_threshold: f
     return keep, count
 
 
-def apply_nms(boxes_xywha: torch.Tensor, scores: torch.Tensor, iou_threshold: float = 0.2) -> torch.Tensor:
-    """utils.py:259-274 → torchvision CPU nms semantics on axis-aligned corners (bit-exact keep set/order)."""
+def apply_nms(boxes_xywha: torch.Tensor, scores: torch.Tensor, iou_threshold: float = 0.2,
+              rotated: bool = False) -> torch.Tensor:
+    """utils.py:259-274 → torchvision CPU nms semantics on axis-aligned corners (bit-exact keep set/order).
+    ``rotated=True``: the same greedy walk with the suppression test on the rotated boxes, box p
+    suppresses a later q iff compute_rotated_iou(sorted, sorted)[p, q] > iou_threshold (bit for bit)."""
     if boxes_xywha.shape[0] == 0:
         return torch.empty((0,), dtype=torch.long, device=boxes_xywha.device)
+    if rotated:
+        return nms_batched([boxes_xywha], [scores], iou_threshold, rotated=True)[0]
     keep, count = nms_device(boxes_xywha, scores, iou_threshold)
     return keep[: int(count.item())]
 
 
-def nms_batched(boxes_list, scores_list, iou_threshold: float = 0.2):
+def nms_batched(boxes_list, scores_list, iou_threshold: float = 0.2, rotated: bool = False):
     """apply_nms for every sample of a batch: one launch per NMS stage for all samples
     (ivit_nms_batched) and one host read of the kept counts. Returns per-sample kept LOCAL
-    indices (int64 device tensors, descending-score order, torchvision CPU semantics)."""
+    indices (int64 device tensors, descending-score order, torchvision CPU semantics).
+    ``rotated=True`` suppresses on the rotated IoU (ivit_nms_rotated_batched; boxes need 5 columns)."""
     ns = [int(b.shape[0]) for b in boxes_list]
     S, total = len(ns), sum(ns)
     dev = boxes_list[0].device if S else torch.device("cuda")
@@ -108,19 +114,24 @@ def nms_batched(boxes_list, scores_list, iou_threshold: float = 0.2):
     moff = np.concatenate([[0], np.cumsum(words)[:-1]]).astype(np.int64)
     b = torch.cat([x.float() for x in boxes_list]).contiguous()
     sc = torch.cat([x.float() for x in scores_list]).contiguous()
+    if rotated and b.shape[1] != 5:
+        raise ValueError(f"rotated NMS takes (n, 5) xywha boxes, got {tuple(b.shape)}")
+    ws_fn, fn = ((lib.ivit_nms_rotated_batched_workspace, lib.ivit_nms_rotated_batched) if rotated else
+                 (lib.ivit_nms_batched_workspace, lib.ivit_nms_batched))
     d_seg = torch.from_numpy(seg).to(dev, non_blocking=True)
     d_moff = torch.from_numpy(moff).to(dev, non_blocking=True)
     keep = torch.empty((total,), dtype=torch.int64, device=dev)
     count = torch.empty((S,), dtype=torch.int64, device=dev)
-    ws = workspace(lib.ivit_nms_batched_workspace(S, total, sum(words)), dev)
-    lib.ivit_nms_batched(ptr(b), ptr(sc), ptr(d_seg), ptr(d_moff), S, total, max(ns), sum(words),
-                         float(iou_threshold), ptr(keep), ptr(count), ptr(ws), ws.numel(), stream())
+    ws = workspace(ws_fn(S, total, sum(words)), dev)
+    fn(ptr(b), ptr(sc), ptr(d_seg), ptr(d_moff), S, total, max(ns), sum(words), float(iou_threshold), ptr(keep),
+       ptr(count), ptr(ws), ws.numel(), stream())
     cnt = count.cpu().tolist()
     return [keep[seg[i]: seg[i] + cnt[i]] for i in range(S)]
 
 
-def _post_launch(cls_logits, box_preds_rel, intent_logits, anchors, conf_threshold, nms_threshold):
-    """ivit_eval_post for a batch on the current stream; returns what _post_collect needs."""
+def _post_launch(cls_logits, box_preds_rel, intent_logits, anchors, conf_threshold, nms_threshold, rotated_nms=False):
+    """ivit_eval_post (ivit_eval_post_rotated with ``rotated_nms``) for a batch on the current stream;
+    returns what _post_collect needs."""
     B, NA = cls_logits.shape[0], anchors.shape[0]
     dev = cls_logits.device
     cls = cls_logits.reshape(B, NA).float().contiguous()  # no copy for the model's f32 outputs
@@ -132,9 +143,11 @@ def _post_launch(cls_logits, box_preds_rel, intent_logits, anchors, conf_thresho
     bx = torch.empty((B, NA, 5), dtype=torch.float32, device=dev)
     ii = torch.empty((B, NA), dtype=torch.int64, device=dev)
     cnt = torch.empty((B,), dtype=torch.int64, device=dev)
-    ws = workspace(lib.ivit_eval_post_workspace(B, NA), dev)
-    lib.ivit_eval_post(ptr(cls), ptr(box), ptr(it), ptr(anc), B, NA, K, float(conf_threshold), float(nms_threshold),
-                       ptr(sc), ptr(bx), ptr(ii), ptr(cnt), ptr(ws), ws.numel(), stream())
+    ws_fn, fn = ((lib.ivit_eval_post_rotated_workspace, lib.ivit_eval_post_rotated) if rotated_nms else
+                 (lib.ivit_eval_post_workspace, lib.ivit_eval_post))
+    ws = workspace(ws_fn(B, NA), dev)
+    fn(ptr(cls), ptr(box), ptr(it), ptr(anc), B, NA, K, float(conf_threshold), float(nms_threshold), ptr(sc), ptr(bx),
+       ptr(ii), ptr(cnt), ptr(ws), ws.numel(), stream())
     return sc, bx, ii, cnt
 
 
@@ -151,17 +164,19 @@ def _post_empty(B, dev):
 
 
 def postprocess_batch(cls_logits: torch.Tensor, box_preds_rel: torch.Tensor, intent_logits: torch.Tensor,
-                      anchors: torch.Tensor, conf_threshold: float = 0.1, nms_threshold: float = 0.2):
+                      anchors: torch.Tensor, conf_threshold: float = 0.1, nms_threshold: float = 0.2,
+                      rotated_nms: bool = False):
     """eval_vit.py:156-176 for a whole batch on hand-written kernels (ivit_eval_post): sigmoid →
     score >= conf in anchor order → decode → NMS → argmax intention, every sample at once, four
     launches and ONE host read (the kept counts). Returns [{'pred_scores', 'pred_boxes_xywha',
     'pred_intentions'}] per sample as device tensors (views of the packed outputs; the caller
-    moves them to the host when it needs them)."""
+    moves them to the host when it needs them). ``rotated_nms=True`` suppresses on the rotated
+    IoU of the decoded boxes (apply_nms(rotated=True)); everything else is the same."""
     B, NA = cls_logits.shape[0], anchors.shape[0]
     if NA == 0 or B == 0:
         return _post_empty(B, cls_logits.device)
     return _post_collect(_post_launch(cls_logits, box_preds_rel, intent_logits, anchors, conf_threshold,
-                                      nms_threshold))
+                                      nms_threshold, rotated_nms))
 
 
 class PostPipeline:
@@ -170,10 +185,13 @@ class PostPipeline:
     are read once batch k+1's forward is enqueued — so the post-processing (sort, NMS mask and walk,
     ~4 ms of mostly serial kernels per B = 32 batch) no longer idles the ViT streams.
     ``push(cls, box, intent)`` returns the previous batch's predictions (None for the first);
-    ``flush()`` returns the last one's. Same kernels and results as postprocess_batch."""
+    ``flush()`` returns the last one's. Same kernels and results as postprocess_batch
+    (``rotated_nms`` included)."""
 
-    def __init__(self, anchors, conf_threshold=0.1, nms_threshold=0.2):
+    def __init__(self, anchors, conf_threshold=0.1, nms_threshold=0.2, rotated_nms=False):
         self.anchors, self.conf, self.nms = anchors, conf_threshold, nms_threshold
+        self.rotated_nms = bool(rotated_nms)
+        self._kw = {"rotated_nms": True} if self.rotated_nms else {}  # the default call is the one it always was
         self.stream = torch.cuda.Stream(anchors.device) if anchors.is_cuda else None
         if self.stream is not None:
             anchors.record_stream(self.stream)
@@ -197,13 +215,15 @@ class PostPipeline:
             self.pending = _post_empty(B, cls_logits.device)
             return prev
         if self.stream is None:
-            self.pending = _post_launch(cls_logits, box_preds_rel, intent_logits, self.anchors, self.conf, self.nms)
+            self.pending = _post_launch(cls_logits, box_preds_rel, intent_logits, self.anchors, self.conf, self.nms,
+                                        **self._kw)
             return prev
         self.stream.wait_stream(torch.cuda.current_stream(cls_logits.device))  # this batch's forward
         for t in (cls_logits, box_preds_rel, intent_logits):
             t.record_stream(self.stream)
         with torch.cuda.stream(self.stream):
-            self.pending = _post_launch(cls_logits, box_preds_rel, intent_logits, self.anchors, self.conf, self.nms)
+            self.pending = _post_launch(cls_logits, box_preds_rel, intent_logits, self.anchors, self.conf, self.nms,
+                                        **self._kw)
         return prev
 
     def flush(self):
