@@ -280,7 +280,7 @@ def test_patch_embed_patch16(cd, B, C, H, W, D):
     w = torch.randn(D, C, 16, 16) / math.sqrt(C * 256)
     b, pos, cls = torch.randn(D) * 0.1, torch.randn(1, (H // 16) * (W // 16) + 1, D) * 0.1, torch.randn(1, 1, D)
     wd = w.to(DEV).requires_grad_(True)
-    out = ops.PatchEmbedFn.apply(img.to(DEV), wd, b.to(DEV), pos.to(DEV), cls.to(DEV), cdt)
+    out = ops.PatchEmbedGenericFn.apply(img.to(DEV), wd, b.to(DEV), pos.to(DEV), cls.to(DEV), cdt)
     imr, wr = img.double(), w.double()
     if cd == torch.bfloat16:
         imr, wr = img.bfloat16().double(), w.bfloat16().double()

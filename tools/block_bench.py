@@ -1,5 +1,5 @@
 """Isolated timing of every token-GEMM kernel of one bf16 ViT block at the bench shape
-(M = 8 x 4501 tokens, D = 384, MLP 1536) exactly as ops.ViTBlockFn launches them, with each
+(M = 8 x 4501 tokens, D = 384, MLP 1536) exactly as ops.ViTBlockPanelFn launches them, with each
 kernel's HBM floor (algorithmic bytes / 6.3 TB/s achievable) and MFMA floor (flops / 2516.6 TF/s).
 python tools/block_bench.py"""
 import os

@@ -125,7 +125,7 @@ def comm_stream_collectives_ok(version=None, env=None):
 
 class GradSink:
     """A parameter's slot in the gradient buckets, for ops that write the gradient themselves
-    (ops.ViTBlockFn: the block's weight / bias / LayerNorm gradients): ``claim()`` -> the bucket view
+    (ops.ViTBlockPanelFn: the block's weight / bias / LayerNorm gradients): ``claim()`` -> the bucket view
     to overwrite (None when the view is not freshly zeroed this step, e.g. a second backward
     without zero_grad — the op then returns its gradient to autograd, which adds it), ``done()``
     after the writes are enqueued on the current stream (the bucket bookkeeping of the

@@ -2,7 +2,7 @@
 signatures, attributes and state_dict keys (model_vit.py:1-184), running on the MI355X
 HIP kernels.
 
-``IntentNetViT.forward`` = 2 x (PatchEmbedFn + 12 ViTBlockFn) + NeckFn (final norms,
+``IntentNetViT.forward`` = 2 x (PatchEmbedFn + 12 ViTBlockPanelFn / ViTBlockFn) + NeckFn (final norms,
 adapters, fusion, both heads). ``set_compute_dtype(torch.bfloat16)`` selects the bf16 MFMA
 path (f32 master weights, f32 residual stream / statistics / loss); the default f32 path is
 the exact-f32 parity path.

@@ -5,7 +5,10 @@ streams and autograd plumbing; there is no eager/ATen fallback for the compute.
 
 Granularity (fused for HBM traffic and launch count, coarse enough for DDP overlap):
   * ``PatchEmbedFn``  timm PatchEmbed + CLS + pos_embed            (model_vit.py:64,71 → timm)
-  * ``ViTBlockFn``    one pre-norm transformer block                (timm Block, ×12 per stream)
+                      (patch 8; ``PatchEmbedGenericFn`` for the other patch sizes)
+  * ``ViTBlockPanelFn`` / ``ViTBlockFn``  one pre-norm transformer block (timm Block, ×12 per
+                      stream): the bf16 D = 384 row-panel path / the engine path for f32 and the
+                      other bf16 widths (``block_on_panel`` picks)
   * ``NeckFn``        final norms + adapters + fusion BasicBlocks + heads
                       (model_vit.py:116-142, 179-185; heads.py)
   * ``DetLossFn``     DetectionIntentionLoss                        (loss.py:58-206)
@@ -582,6 +585,38 @@ def bn_backward(x, y, dy, st, g, relu, out_dtype, want_dr=False):
 
 
 # ------------------------------------------------------------------------------ fused Functions
+class PatchEmbedGenericFn(torch.autograd.Function):
+    """PatchEmbedFn for the other patch sizes (timm vit_*_patch16_224 at model_vit.py:64,71): the
+    patch matrix in the compute dtype, the linear GEMM, then the CLS / pos_embed assembly
+    (ivit_patch_*). Takes no hand-off: its backward reads the f32 dtok."""
+
+    @staticmethod
+    def forward(ctx, img, w, b, pos, cls, cdt):
+        B, C, H, W = img.shape
+        D, P = w.shape[0], w.shape[-1]
+        Np = (H // P) * (W // P)
+        cols = torch.empty((B * Np, C * P * P), dtype=tdtype(cdt), device=img.device)
+        lib.ivit_patch_im2col_p(ptr(img), B, C, H, W, P, ptr(cols), cdt, stream())
+        y, _ = linear_fwd(cols, cast_weight(w, tdtype(cdt)).reshape(D, C * P * P), b, cdt, out_dtype=torch.float32)
+        out = torch.empty((B * (Np + 1), D), dtype=torch.float32, device=img.device)
+        lib.ivit_patch_tokens(ptr(y), B, Np, D, ptr(pos), ptr(cls), ptr(out), stream())
+        ctx.save_for_backward(cols)
+        ctx.meta = (B, Np, D, cdt, w.shape)
+        return out
+
+    @staticmethod
+    def backward(ctx, dtok):
+        (cols,) = ctx.saved_tensors
+        B, Np, D, cdt, wshape = ctx.meta
+        dtok = dtok.contiguous()
+        dy = torch.empty((B * Np, D), dtype=tdtype(cdt), device=cols.device)
+        dpos = torch.empty((1, Np + 1, D), dtype=torch.float32, device=cols.device)
+        dcls = torch.empty((1, 1, D), dtype=torch.float32, device=cols.device)
+        lib.ivit_patch_tokens_bwd(ptr(dtok), dt(dtok), B, Np, D, ptr(dy), cdt, ptr(dpos), ptr(dcls), 0, stream())
+        dw, db = linear_wgrad(dy, cols, cdt)
+        return None, dw.reshape(wshape), db, dpos, dcls, None
+
+
 class PatchEmbedFn(torch.autograd.Function):
     """timm PatchEmbed(Conv2d k=s=8, bias) → flatten/transpose → cat(CLS) → +pos_embed.
     img (B, C, H, W) f32 → tokens (B*(Np+1), D) f32. No input gradient (the BEV raster)."""
@@ -590,27 +625,12 @@ class PatchEmbedFn(torch.autograd.Function):
     def forward(ctx, img, w, b, pos, cls, cdt, hand=None):
         B, C, H, W = img.shape
         D = w.shape[0]
-        P = w.shape[-1]
+        assert w.shape[-1] == 8, "patch-8 kernels; other patch sizes: PatchEmbedGenericFn"
         # hand (GradHandoff): block 0's qkv-dgrad + norm1-backward epilogue also writes bf16(dtok),
         # the weight gradient's operand, so the backward skips its own cast pass over dtok
         ctx.hand = hand
         if hand is not None:
             hand.scale, hand.g, hand.key = None, None, None
-        if P != 8:
-            # other patch sizes (timm vit_*_patch16_224 at model_vit.py:64,71): patch matrix in the
-            # compute dtype, the linear GEMM, then the CLS / pos_embed assembly (ivit_patch_*)
-            Np = (H // P) * (W // P)
-            cols = torch.empty((B * Np, C * P * P), dtype=tdtype(cdt), device=img.device)
-            lib.ivit_patch_im2col_p(ptr(img), B, C, H, W, P, ptr(cols), cdt, stream())
-            y, _ = linear_fwd(cols, cast_weight(w, tdtype(cdt)).reshape(D, C * P * P), b, cdt,
-                              out_dtype=torch.float32)
-            out = torch.empty((B * (Np + 1), D), dtype=torch.float32, device=img.device)
-            lib.ivit_patch_tokens(ptr(y), B, Np, D, ptr(pos), ptr(cls), ptr(out), stream())
-            ctx.save_for_backward(cols)
-            ctx.meta = (B, C, H, W, D, cdt, w.shape)
-            ctx.generic = True
-            return out
-        ctx.generic = False
         Ntok = (H // 8) * (W // 8) + 1
         wc = cast_weight(w, tdtype(cdt)).reshape(D, C * 64)
         out = torch.empty((B * Ntok, D), dtype=torch.float32, device=img.device)
@@ -643,16 +663,6 @@ class PatchEmbedFn(torch.autograd.Function):
     def backward(ctx, dtok):
         (src,) = ctx.saved_tensors
         B, C, H, W, D, cdt, wshape = ctx.meta
-        if ctx.generic:
-            P = wshape[-1]
-            Np = (H // P) * (W // P)
-            dtok = dtok.contiguous()
-            dy = torch.empty((B * Np, D), dtype=tdtype(cdt), device=src.device)
-            dpos = torch.empty((1, Np + 1, D), dtype=torch.float32, device=src.device)
-            dcls = torch.empty((1, 1, D), dtype=torch.float32, device=src.device)
-            lib.ivit_patch_tokens_bwd(ptr(dtok), dt(dtok), B, Np, D, ptr(dy), cdt, ptr(dpos), ptr(dcls), 0, stream())
-            dw, db = linear_wgrad(dy, src, cdt)
-            return None, dw.reshape(wshape), db, dpos, dcls, None, None
         hd = ctx.hand
         if hd is not None and hd.g is not None and hd.g.dtype == tdtype(cdt) and hd.key == GradHandoff.ident(dtok):
             dtok = hd.g  # written by block 0's backward (unmodified dtok: same tensor and version)
@@ -708,141 +718,154 @@ def grad_sinks(params):
     return sinks, views
 
 
-class ViTBlockFn(torch.autograd.Function):
-    """timm Block: x + dp1(proj(attn(norm1 x))); x + dp2(fc2(gelu(fc1(norm2 x)))).
-    x: (B*N, D) f32 residual stream; GEMM operands in the compute dtype (f32 or bf16).
+def block_on_panel(cdt, D):
+    """Which Function runs a timm Block of width D in compute dtype cdt: the row-panel kernels
+    (ViTBlockPanelFn) are built for bf16 at D = 384; everything else takes ViTBlockFn."""
+    return cdt == BF16 and D == 384
 
-    bf16 row-panel fusion (D = 384): the proj GEMM's epilogue also applies norm2, and — when
-    the NEXT block's norm1 parameters are passed (nxw, nxb) — the fc2 GEMM's epilogue applies
-    that norm1 too and returns (y, mean, rstd) as extra, non-differentiable outputs. The next
-    block takes them as (ln_in, m_in, r_in) instead of running its norm1 and still does that
-    LayerNorm's backward itself (from its input x and the handed-over statistics), exactly as
-    in the unfused block. Without fusion the extra outputs are empty tensors."""
+
+class ViTBlockPanelFn(torch.autograd.Function):
+    """timm Block: x + dp1(proj(attn(norm1 x))); x + dp2(fc2(gelu(fc1(norm2 x)))), bf16 at D = 384
+    on the row-panel kernels (block_on_panel). x: (B*N, D) f32 residual stream; the GEMMs read the
+    packed f32 master weights.
+
+    The proj GEMM's epilogue also applies norm2, and — when the NEXT block's norm1 parameters are
+    passed (nxw, nxb) — the fc2 GEMM's epilogue applies that norm1 too and returns (y, mean, rstd)
+    as extra, non-differentiable outputs (empty tensors otherwise). The next block takes them as
+    (ln_in, m_in, r_in) instead of running its norm1 and still does that LayerNorm's backward
+    itself (from its input x and the handed-over statistics), exactly as in the unfused block."""
 
     @staticmethod
     def forward(ctx, x, ln_in, m_in, r_in, n1w, n1b, qkvw, qkvb, pw, pb, n2w, n2b, f1w, f1b, f2w, f2b, nxw, nxb,
                 s1, s2, meta, hand_mine=None, hand_prev=None):
-        B, N, H, cdt, eps = meta
-        cd = tdtype(cdt)
-        q2 = cdt == BF16
-        panel = q2 and x.shape[1] == 384
-        if panel:  # row-panel kernels read the packed weights
-            wq = wp = w1 = w2 = None
-        else:
-            wq, wp, w1, w2 = cast_weight(qkvw, cd), cast_weight(pw, cd), cast_weight(f1w, cd), cast_weight(f2w, cd)
+        B, N, H, _, eps = meta
         if ln_in is None:
-            ln1, m1, r1 = layernorm_fwd(x, n1w, n1b, eps, cd)
+            ln1, m1, r1 = layernorm_fwd(x, n1w, n1b, eps, torch.bfloat16)
         else:
             ln1, m1, r1 = ln_in, m_in, r_in
-        if panel:
-            qkv, _ = panel_fwd(ln1, qkvw, qkvb, qcols=H * 64, qscale=Q2_SCALE)
-            o, lse = attn_fwd_q2(qkv, B, N, H)
-        elif q2:
-            qkv = qkv_fwd_q2(ln1, wq, qkvb, H * 64)
-            o, lse = attn_fwd_q2(qkv, B, N, H)
-        else:
-            qkv, _ = linear_fwd(ln1, wq, qkvb, cdt)
-            o, lse = attn_fwd(qkv, B, N, H, cdt)
-        if panel:
-            x1, ln2, m2, r2 = linear_resid_ln_fwd(o, pw, pb, x, s1, N, n2w, n2b, eps)
-        else:
-            x1, _ = linear_fwd(o, wp, pb, cdt, resid=x, row_scale=s1, rps=N)
-            ln2, m2, r2 = layernorm_fwd(x1, n2w, n2b, eps, cd)
-        # inference (torch.inference_mode): nothing is saved, and fc1 skips its pre-activation copy
+        qkv, _ = panel_fwd(ln1, qkvw, qkvb, qcols=H * 64, qscale=Q2_SCALE)
+        o, lse = attn_fwd_q2(qkv, B, N, H)
+        x1, ln2, m2, r2 = linear_resid_ln_fwd(o, pw, pb, x, s1, N, n2w, n2b, eps)
+        # inference (torch.inference_mode): nothing is saved, and fc1 skips its pre-activation copy.
+        # training: h = GELU'(fc1 pre-activation) for the fc2 dgrad (panel_dgrad_mul), computed
+        # beside GELU from the f32 pre-activation instead of re-evaluated in the backward
         infer = torch.is_inference_mode_enabled()
-        if panel:
-            # training: h = GELU'(fc1 pre-activation) for the fc2 dgrad (panel_dgrad_mul), computed
-            # beside GELU from the f32 pre-activation instead of re-evaluated in the backward
-            a, h = panel_fwd(ln2, f1w, f1b, act=ACT_GELU if infer else ACT_GELU_D, want_pre=not infer)
-        else:
-            a, h = linear_fwd(ln2, w1, f1b, cdt, act=ACT_GELU, want_pre=not infer)
-        if nxw is not None and panel:
+        a, h = panel_fwd(ln2, f1w, f1b, act=ACT_GELU if infer else ACT_GELU_D, want_pre=not infer)
+        if nxw is not None:
             x2, lnx, mx, rx = linear_resid_ln_fwd(a, f2w, f2b, x1, s2, N, nxw, nxb, eps)
-        elif panel:
+        else:
             # the last block: the same row-panel residual GEMM (its LayerNorm epilogue on unit
             # parameters, outputs discarded) instead of the 128 x 128 engine's EpiResid GEMM
             g1, b0 = _unit_ln_params(x.shape[1], x.device)
             x2 = linear_resid_ln_fwd(a, f2w, f2b, x1, s2, N, g1, b0, eps)[0]
             lnx = mx = rx = x2.new_empty(0)
-        else:
-            x2, _ = linear_fwd(a, w2, f2b, cdt, resid=x1, row_scale=s2, rps=N)
-            lnx = mx = rx = x2.new_empty(0)
         ctx.mark_non_differentiable(lnx, mx, rx)
         ctx.set_materialize_grads(False)  # no zero-filled gradients for the three extra outputs
         if infer:
-            ctx.meta, ctx.q2 = meta, q2
             return x2, lnx, mx, rx
-        ctx.save_for_backward(x, ln1, qkv, o, lse, x1, ln2, h, a, m1, r1, m2, r2, n1w, n2w, wq, wp, w1, w2, s1, s2,
-                              qkvw, f1w, f2w, pw)
+        ctx.save_for_backward(x, ln1, qkv, o, lse, x1, ln2, h, a, m1, r1, m2, r2, n1w, n2w, s1, s2, qkvw, f1w, f2w,
+                              pw)
         ctx.meta = meta
-        ctx.q2 = q2
-        ctx.panel = panel
         # the parameters themselves (not saved tensors): their gradient-bucket sinks, if any
         ctx.params = (n1w, n1b, qkvw, qkvb, pw, pb, n2w, n2b, f1w, f1b, f2w, f2b)
-        ctx.hand_mine, ctx.hand_prev = (hand_mine, hand_prev) if panel else (None, None)
-        if ctx.hand_mine is not None:
-            ctx.hand_mine.scale, ctx.hand_mine.g, ctx.hand_mine.key = s2, None, None
+        ctx.hand_mine, ctx.hand_prev = hand_mine, hand_prev
+        if hand_mine is not None:
+            hand_mine.scale, hand_mine.g, hand_mine.key = s2, None, None
         return x2, lnx, mx, rx
 
     @staticmethod
     def backward(ctx, dx2, *_unused):
-        (x, ln1, qkv, o, lse, x1, ln2, h, a, m1, r1, m2, r2, n1w, n2w, wq, wp, w1, w2, s1, s2, qkvw,
-         f1w, f2w, pw) = ctx.saved_tensors
-        B, N, H, cdt, eps = ctx.meta
-        cd = tdtype(cdt)
+        (x, ln1, qkv, o, lse, x1, ln2, h, a, m1, r1, m2, r2, n1w, n2w, s1, s2, qkvw, f1w, f2w,
+         pw) = ctx.saved_tensors
+        B, N, H, _, _ = ctx.meta
+        cd = torch.bfloat16
         dx2 = torch.zeros_like(x) if dx2 is None else dx2.contiguous()
-        D = x.shape[1]
         hm, hp = ctx.hand_mine, ctx.hand_prev
         dx2s = None
         if hm is not None:
-            if hm.g is not None and dx2 is not None and hm.key == GradHandoff.ident(dx2):
+            if hm.g is not None and hm.key == GradHandoff.ident(dx2):
                 dx2s = hm.g  # written by the next block's qkv-dgrad epilogue
                 GradHandoff.used += 1
             hm.g = hm.key = None
         if dx2s is None:
-            dx2s = add_act_grad(dx2, row_scale=s2, row_elems=N * D, out_dtype=cd)
-        dh = panel_dgrad_mul(dx2s, f2w, h) if ctx.panel else linear_dgrad(dx2s, w2, cdt, cd, gelu_pre=h)
-        # bf16 row-panel blocks: the four weight gradients in one grouped launch after the dgrads
-        # (ivit_vit_block_wgrad) instead of four split-K engine GEMMs (-1.5 ms per step, round 3)
-        group = ctx.panel
+            dx2s = add_act_grad(dx2, row_scale=s2, row_elems=N * x.shape[1], out_dtype=cd)
+        dh = panel_dgrad_mul(dx2s, f2w, h)
         # DDP: the twelve parameter gradients straight into their bucket views (no autograd add)
-        direct = grad_sinks(ctx.params) if group else None
+        direct = grad_sinks(ctx.params)
         dv = direct[1] if direct is not None else [None] * 12
-        g2 = None if group else linear_wgrad(dx2s, a, cdt)
-        if ctx.panel:  # fc1 dgrad with norm2's backward in the epilogue
-            dx1, dx1s, dg2, dbe2 = linear_dgrad_ln_bwd(dh, f1w, x1, n2w, m2, r2, dres=dx2, dx=torch.empty_like(dx2),
-                                                       xs_dtype=cd, row_scale=s1, rps=N, dg=dv[6], db=dv[7])
+        # fc1 dgrad with norm2's backward in the epilogue
+        dx1, dx1s, dg2, dbe2 = linear_dgrad_ln_bwd(dh, f1w, x1, n2w, m2, r2, dres=dx2, dx=torch.empty_like(dx2),
+                                                   xs_dtype=cd, row_scale=s1, rps=N, dg=dv[6], db=dv[7])
+        do = panel_dgrad(dx1s, pw)
+        dqkv = attn_bwd_q2(qkv, o, do, lse, B, N, H)
+        # qkv dgrad with norm1's backward in the epilogue
+        if hp is not None:  # also the previous block's bf16(dx0 * s2) (GradHandoff)
+            dx0, dx0s, dg1, dbe1 = linear_dgrad_ln_bwd(dqkv, qkvw, x, n1w, m1, r1, dres=dx1, dx=dx1, xs_dtype=cd,
+                                                       row_scale=hp.scale, rps=N, dg=dv[0], db=dv[1])
+            hp.g, hp.key = dx0s, GradHandoff.ident(dx0)
         else:
-            dln2 = linear_dgrad(dh, w1, cdt, torch.float32)
-            dx1, dx1s, dg2, dbe2 = layernorm_bwd(x1, n2w, m2, r2, dln2, dres=dx2, dx=torch.empty_like(dx2),
-                                                 xs_dtype=cd, row_scale=s1, rps=N)
-        g1 = None if group else linear_wgrad(dh, ln2, cdt)
-        do = panel_dgrad(dx1s, pw) if ctx.panel else linear_dgrad(dx1s, wp, cdt, cd)
-        gp = None if group else linear_wgrad(dx1s, o, cdt)
-        dqkv = attn_bwd_q2(qkv, o, do, lse, B, N, H) if ctx.q2 else attn_bwd(qkv, o, do, lse, B, N, H, cdt)
-        if ctx.panel:  # qkv dgrad with norm1's backward in the epilogue
-            if hp is not None:  # also the previous block's bf16(dx0 * s2) (GradHandoff)
-                dx0, dx0s, dg1, dbe1 = linear_dgrad_ln_bwd(dqkv, qkvw, x, n1w, m1, r1, dres=dx1, dx=dx1, xs_dtype=cd,
-                                                           row_scale=hp.scale, rps=N, dg=dv[0], db=dv[1])
-                hp.g, hp.key = dx0s, GradHandoff.ident(dx0)
-            else:
-                dx0, _, dg1, dbe1 = linear_dgrad_ln_bwd(dqkv, qkvw, x, n1w, m1, r1, dres=dx1, dx=dx1, dg=dv[0],
-                                                        db=dv[1])
-        else:
-            dln1 = linear_dgrad(dqkv, wq, cdt, torch.float32)
-            dx0, _, dg1, dbe1 = layernorm_bwd(x, n1w, m1, r1, dln1, dres=dx1, dx=dx1)
-        if group:
-            outs = None if direct is None else (dv[10], dv[11], dv[8], dv[9], dv[4], dv[5], dv[2], dv[3])
-            g2, g1, gp, gq = vit_block_wgrad(dx2s, a, dh, ln2, dx1s, o, dqkv, ln1, outs=outs)
-        else:
-            gq = linear_wgrad(dqkv, ln1, cdt)
+            dx0, _, dg1, dbe1 = linear_dgrad_ln_bwd(dqkv, qkvw, x, n1w, m1, r1, dres=dx1, dx=dx1, dg=dv[0], db=dv[1])
+        # the four weight gradients in one grouped launch after the dgrads (ivit_vit_block_wgrad)
+        # instead of four split-K engine GEMMs (-1.5 ms per step, round 3)
+        outs = None if direct is None else (dv[10], dv[11], dv[8], dv[9], dv[4], dv[5], dv[2], dv[3])
+        g2, g1, gp, gq = vit_block_wgrad(dx2s, a, dh, ln2, dx1s, o, dqkv, ln1, outs=outs)
+        grads = (dg1, dbe1, *gq, *gp, dg2, dbe2, *g1, *g2)
         if direct is not None:  # written into the buckets: nothing for autograd to accumulate
             for sk in direct[0]:
                 sk.done()
-            return (dx0,) + (None,) * 22
-        (dW2, db2), (dW1, db1), (dWp, dbp), (dWq, dbq) = g2, g1, gp, gq
-        return (dx0, None, None, None, dg1, dbe1, dWq, dbq, dWp, dbp, dg2, dbe2, dW1, db1, dW2, db2, None, None,
-                None, None, None, None, None)
+            grads = (None,) * 12
+        return (dx0, None, None, None) + grads + (None,) * 7
+
+
+class ViTBlockFn(torch.autograd.Function):
+    """The same timm Block on the engine GEMMs, for f32 (the parity path) and for bf16 at the
+    widths the row-panel kernels do not cover (vit_tiny_*, D = 192): compute-dtype copies of the
+    weights (cast_weight), LayerNorm as kernels of its own, four split-K weight gradients.
+    bf16 runs attention on the prescaled Q (qkv_fwd_q2 + the _q2 entries), f32 the plain entries."""
+
+    @staticmethod
+    def forward(ctx, x, n1w, n1b, qkvw, qkvb, pw, pb, n2w, n2b, f1w, f1b, f2w, f2b, s1, s2, meta):
+        B, N, H, cdt, eps = meta
+        cd = tdtype(cdt)
+        wq, wp, w1, w2 = cast_weight(qkvw, cd), cast_weight(pw, cd), cast_weight(f1w, cd), cast_weight(f2w, cd)
+        ln1, m1, r1 = layernorm_fwd(x, n1w, n1b, eps, cd)
+        if cdt == BF16:
+            qkv = qkv_fwd_q2(ln1, wq, qkvb, H * 64)
+            o, lse = attn_fwd_q2(qkv, B, N, H)
+        else:
+            qkv, _ = linear_fwd(ln1, wq, qkvb, cdt)
+            o, lse = attn_fwd(qkv, B, N, H, cdt)
+        x1, _ = linear_fwd(o, wp, pb, cdt, resid=x, row_scale=s1, rps=N)
+        ln2, m2, r2 = layernorm_fwd(x1, n2w, n2b, eps, cd)
+        # inference (torch.inference_mode): nothing is saved, and fc1 skips its pre-activation copy
+        infer = torch.is_inference_mode_enabled()
+        a, h = linear_fwd(ln2, w1, f1b, cdt, act=ACT_GELU, want_pre=not infer)
+        x2, _ = linear_fwd(a, w2, f2b, cdt, resid=x1, row_scale=s2, rps=N)
+        if not infer:
+            ctx.save_for_backward(x, ln1, qkv, o, lse, x1, ln2, h, a, m1, r1, m2, r2, n1w, n2w, wq, wp, w1, w2, s1, s2)
+            ctx.meta = meta
+        return x2
+
+    @staticmethod
+    def backward(ctx, dx2):
+        x, ln1, qkv, o, lse, x1, ln2, h, a, m1, r1, m2, r2, n1w, n2w, wq, wp, w1, w2, s1, s2 = ctx.saved_tensors
+        B, N, H, cdt, _ = ctx.meta
+        cd = tdtype(cdt)
+        dx2 = dx2.contiguous()
+        dx2s = add_act_grad(dx2, row_scale=s2, row_elems=N * x.shape[1], out_dtype=cd)
+        dh = linear_dgrad(dx2s, w2, cdt, cd, gelu_pre=h)
+        dW2, db2 = linear_wgrad(dx2s, a, cdt)
+        dln2 = linear_dgrad(dh, w1, cdt, torch.float32)
+        dx1, dx1s, dg2, dbe2 = layernorm_bwd(x1, n2w, m2, r2, dln2, dres=dx2, dx=torch.empty_like(dx2), xs_dtype=cd,
+                                             row_scale=s1, rps=N)
+        dW1, db1 = linear_wgrad(dh, ln2, cdt)
+        do = linear_dgrad(dx1s, wp, cdt, cd)
+        dWp, dbp = linear_wgrad(dx1s, o, cdt)
+        dqkv = attn_bwd_q2(qkv, o, do, lse, B, N, H) if cdt == BF16 else attn_bwd(qkv, o, do, lse, B, N, H, cdt)
+        dln1 = linear_dgrad(dqkv, wq, cdt, torch.float32)
+        dx0, _, dg1, dbe1 = layernorm_bwd(x, n1w, m1, r1, dln1, dres=dx1, dx=dx1)
+        dWq, dbq = linear_wgrad(dqkv, ln1, cdt)
+        return dx0, dg1, dbe1, dWq, dbq, dWp, dbp, dg2, dbe2, dW1, db1, dW2, db2, None, None, None
 
 
 _UNIT_LN = {}

@@ -2,7 +2,8 @@
 model_vit.py:64,71): same attribute surface (``patch_embed.grid_size``, ``num_prefix_tokens``,
 ``embed_dim``, ``cls_token``, assignable ``head``, ``forward_features``) and the same
 ``state_dict`` keys as timm's ``vit_{small,tiny}_patch{8,16}_224``, so reference checkpoints load.
-Compute runs in ``ops.PatchEmbedFn`` + ``ops.ViTBlockFn`` (HIP)."""
+Compute runs in ``ops.PatchEmbedFn`` / ``PatchEmbedGenericFn`` + ``ops.ViTBlockPanelFn`` /
+``ViTBlockFn`` (HIP)."""
 from __future__ import annotations
 
 import math
@@ -84,19 +85,21 @@ class Block(nn.Module):
         return self.last_scales
 
     def forward_flat(self, x, B, N, cdt, ln_in=None, next_norm=None, hand_mine=None, hand_prev=None, drawn=None):
-        """-> (x_out, (y, mean, rstd) of the next block's norm1 or empty tensors): `ln_in` is
-        this block's (y, mean, rstd) of norm1 computed by the previous block's fc2 epilogue;
-        `next_norm` the next block's norm1, whose forward this block's fc2 epilogue runs
-        (ops.ViTBlockFn, bf16 row-panel path)."""
+        """-> (x_out, (y, mean, rstd) of the next block's norm1, empty tensors without `next_norm`,
+        None on the engine path). Row-panel path (ops.ViTBlockPanelFn) only: `ln_in` is this
+        block's (y, mean, rstd) of norm1 computed by the previous block's fc2 epilogue; `next_norm`
+        the next block's norm1, whose forward this block's fc2 epilogue runs; the hand-offs."""
         s1, s2 = self._scales(B, x.device, drawn)
+        params = (self.norm1.weight, self.norm1.bias, self.attn.qkv.weight, self.attn.qkv.bias,
+                  self.attn.proj.weight, self.attn.proj.bias, self.norm2.weight, self.norm2.bias,
+                  self.mlp.fc1.weight, self.mlp.fc1.bias, self.mlp.fc2.weight, self.mlp.fc2.bias)
+        meta = (B, N, self.attn.num_heads, cdt, 1e-6)
+        if not ops.block_on_panel(cdt, x.shape[1]):
+            return ops.ViTBlockFn.apply(x, *params, s1, s2, meta), None
         nxw = next_norm.weight if next_norm is not None else None
         nxb = next_norm.bias if next_norm is not None else None
         li, mi, ri = ln_in if ln_in is not None else (None, None, None)
-        out = ops.ViTBlockFn.apply(x, li, mi, ri, self.norm1.weight, self.norm1.bias, self.attn.qkv.weight,
-                                    self.attn.qkv.bias, self.attn.proj.weight, self.attn.proj.bias, self.norm2.weight,
-                                    self.norm2.bias, self.mlp.fc1.weight, self.mlp.fc1.bias, self.mlp.fc2.weight,
-                                    self.mlp.fc2.bias, nxw, nxb, s1, s2, (B, N, self.attn.num_heads, cdt, 1e-6),
-                                    hand_mine, hand_prev)
+        out = ops.ViTBlockPanelFn.apply(x, li, mi, ri, *params, nxw, nxb, s1, s2, meta, hand_mine, hand_prev)
         return out[0], tuple(out[1:])
 
     def forward(self, x):
@@ -168,15 +171,17 @@ class VisionTransformer(nn.Module):
         if (H, W) != self.patch_embed.img_size:
             raise ValueError(f"Input size {(H, W)} != model img_size {self.patch_embed.img_size} (timm strict size)")
         cdt = self._cdt()
-        # bf16 at D = 384: block i's fc2 epilogue also produces block i+1's norm1 (ops.ViTBlockFn)
-        fuse = cdt == BF16 and self.embed_dim == 384
+        # row-panel path: block i's fc2 epilogue also produces block i+1's norm1 (ops.ViTBlockPanelFn)
+        fuse = ops.block_on_panel(cdt, self.embed_dim)
         # ... and in the backward, block i+1 hands block i its DropPath-scaled bf16 gradient, and
         # block 0 hands the patch embedding its bf16 token gradient
         hands = [ops.GradHandoff() for _ in self.blocks] if fuse and torch.is_grad_enabled() else None
-        # (only the fused patch-8 embedding reads it; the generic patch path takes its f32 dtok)
-        hand_pe = ops.GradHandoff() if hands and self.patch_embed.proj.weight.shape[-1] == 8 else None
-        t = ops.PatchEmbedFn.apply(x.float().contiguous(), self.patch_embed.proj.weight, self.patch_embed.proj.bias,
-                                   self.pos_embed, self.cls_token, cdt, hand_pe)
+        # (only the patch-8 embedding reads it; the generic patch path takes its f32 dtok)
+        p8 = self.patch_embed.proj.weight.shape[-1] == 8
+        hand_pe = ops.GradHandoff() if hands and p8 else None
+        pe = (x.float().contiguous(), self.patch_embed.proj.weight, self.patch_embed.proj.bias, self.pos_embed,
+              self.cls_token, cdt)
+        t = ops.PatchEmbedFn.apply(*pe, hand_pe) if p8 else ops.PatchEmbedGenericFn.apply(*pe)
         N = self.patch_embed.num_patches + 1
         ln = None
         drawn = self._draw_drop_path(B, x.device)
