@@ -220,6 +220,23 @@ int ivit_attn_fwd_q2(const void* qkv, long B, long N, long H, long Dh, void* out
 int ivit_attn_bwd_q2(const void* qkv, const void* out, const void* dout, const float* lse, long B, long N, long H,
                      long Dh, void* dqkv, void* work, long work_bytes, void* stream);
 
+/* ---- Attention probabilities of chosen query rows (model_vit.py:64,71 -> timm Attention: the rows
+ *      softmax(q k^T / sqrt(Dh)) that a forward hook on timm's attention would read; the reference
+ *      lists their qualitative analysis as future work). qkv as for ivit_attn_fwd: [B, N, 3, H, Dh]
+ *      rows of 3*H*Dh, IVIT_F32 or IVIT_BF16, 16-byte aligned. Request r < R names the query row
+ *      (sample[r], token[r]) (device int arrays). out (f32): head_mean = 0 -> [R, H, N],
+ *      out[r, h, :] = softmax over all N keys; head_mean = 1 -> [R, N], their mean over the heads,
+ *      summed in head order. q_prescaled = 1 (IVIT_BF16 only): the Q block holds q * log2(e)/sqrt(Dh)
+ *      as ivit_linear_fwd_qs writes it, and the kernel takes exp2 of the raw dot products. Dot
+ *      products and softmax in f32, the row's maximum subtracted, the row normalised by its own sum
+ *      (no saved lse: works from an inference-mode forward); no atomics, bitwise repeatable. No
+ *      workspace: the scores of the first 15 360 keys wait in LDS (60 KB at most, sized from N by the
+ *      launcher), later keys are recomputed, so any N >= 1 runs. A request with sample outside
+ *      [0, B) or token outside [0, N) gets a zero row and reads nothing. R = 0 returns 0 without a
+ *      launch.                                                                                     */
+int ivit_attn_rows(int dtype, const void* qkv, long B, long N, long H, long Dh, int q_prescaled, const int* sample,
+                   const int* token, long R, int head_mean, float* out, void* stream);
+
 /* ---- Kernel execution timing (bench.py's roofline figure; no reference counterpart).
  * While armed, ivit_attn_fwd_q2 / ivit_attn_bwd_q2 launch through hipExtLaunchKernel with a
  * start / stop event pair bound to the kernel itself: HIP stamps them at the kernel's own begin

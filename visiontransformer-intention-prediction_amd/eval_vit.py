@@ -15,13 +15,18 @@ on the device for the whole batch (utils.postprocess_batch, pipelined by utils.P
 walk runs on the device for all samples in one launch (metrics.match_device, ivit_det_match). The reference's undefined names (eval_vit.py:12-13,39,196,219)
 come from constants.py / utils.py. ``--rotated-nms`` (off by default; the reference's future work)
 makes the NMS suppress on the rotated IoU of the decoded boxes instead of their axis-aligned corners.
+``--attn-maps DIR`` (the reference's other future-work item, qualitative analysis of the attention)
+writes, per batch, the attention maps of both ViT streams for each sample's ``--attn-top`` best
+detections at ``--attn-blocks`` (AttnDump; IntentNetViT.attention_maps).
 """
 from __future__ import annotations
 
 import argparse
+import os
 import time
 from pathlib import Path
 
+import numpy as np
 import torch
 
 import model_vit
@@ -80,19 +85,62 @@ def parse_args(argv=None):
                     help="rotated IoU for mAP / matching (device kernel; no shapely needed)")
     ap.add_argument("--rotated-nms", action="store_true", default=EVAL_USE_ROTATED_NMS,
                     help="suppress on the rotated IoU of the decoded boxes (independent of --rotated)")
+    ap.add_argument("--attn-maps", type=str, default=None, metavar="DIR",
+                    help="write the attention maps of each sample's best detections, one .npz per batch (ViT only)")
+    ap.add_argument("--attn-top", type=int, default=8, help="detections per sample (highest score after NMS)")
+    ap.add_argument("--attn-blocks", type=str, default="-1",
+                    help="comma list of ViT block indices, negative from the end")
     return ap.parse_args(argv)
 
 
-def run_inference(model, loader, anchors, conf=CONFIDENCE_THRESHOLD, nms=NMS_IOU_THRESHOLD, rotated_nms=False):
+class AttnDump:
+    """``--attn-maps``: for every sample of a batch, the ``top`` highest-scoring detections after NMS
+    -> the head-mean attention maps of both ViT streams at ``blocks`` for the token under each box
+    centre (IntentNetViT.attention_maps), written to ``out_dir/attn_batch_<k>.npz``:
+      lidar, map [L, R, Hf, Wf]; lidar_cls, map_cls [L, R]; lidar_cells, map_cells [R, 2] (gy, gx);
+      boxes_xywha [R, 5]; scores [R]; sample [R] (index inside the batch); blocks [L].
+    R = the batch's chosen detections, sample-major, best first."""
+
+    def __init__(self, out_dir, top=8, blocks=(-1,)):
+        self.out_dir, self.top, self.blocks = str(out_dir), int(top), tuple(int(b) for b in blocks)
+        if self.top < 1:
+            raise ValueError("--attn-top must be at least 1")
+        os.makedirs(self.out_dir, exist_ok=True)
+        self.written = 0
+
+    def __call__(self, model, lidar_bev, map_bev, preds):
+        sample, boxes, scores = [], [], []
+        for b, p in enumerate(preds):
+            sc = p["pred_scores"].float().cpu()
+            top = torch.topk(sc, min(self.top, sc.numel())).indices
+            sample.append(torch.full((top.numel(),), b, dtype=torch.long))
+            boxes.append(p["pred_boxes_xywha"].float().cpu()[top].reshape(-1, 5))
+            scores.append(sc[top])
+        sample, boxes, scores = torch.cat(sample), torch.cat(boxes), torch.cat(scores)
+        maps = model.attention_maps(lidar_bev, map_bev, sample, boxes[:, :2], blocks=self.blocks, head_mean=True)
+        path = os.path.join(self.out_dir, f"attn_batch_{self.written:05d}.npz")
+        np.savez(path, **{k: v.cpu().numpy() for k, v in maps.items()}, boxes_xywha=boxes.numpy(),
+                 scores=scores.numpy(), sample=sample.numpy(), blocks=np.asarray(self.blocks, dtype=np.int64))
+        self.written += 1
+        return path
+
+
+def run_inference(model, loader, anchors, conf=CONFIDENCE_THRESHOLD, nms=NMS_IOU_THRESHOLD, rotated_nms=False,
+                  attn_dump=None):
     """eval_vit.py:136-180: forward + post-processing per batch, in loader order. The
     post-processing of a batch (utils.PostPipeline) runs beside the next batch's forward; results
     are the per-batch postprocess_batch ones, appended in the same order. ``rotated_nms``: the
-    NMS suppresses on the rotated IoU (utils.apply_nms(rotated=True))."""
+    NMS suppresses on the rotated IoU (utils.apply_nms(rotated=True)). ``attn_dump`` (AttnDump):
+    a batch's inputs are kept until its detections arrive (one batch late), then its attention
+    maps are computed and written; the results are the same with and without it."""
     results = []
     pipe = PostPipeline(anchors, conf, nms, rotated_nms=rotated_nms)
     gts = []
+    held = []  # attn_dump: the (lidar, map) rasters of the batches whose detections are still pending
 
     def emit(preds):
+        if attn_dump is not None:
+            attn_dump(model, *held.pop(0), preds)
         for p, gt in zip(preds, gts.pop(0)):
             results.append({**{k: v.cpu() for k, v in p.items()},
                             "gt_boxes_xywha": gt.get("boxes_xywha", torch.empty((0, 5))),
@@ -101,9 +149,11 @@ def run_inference(model, loader, anchors, conf=CONFIDENCE_THRESHOLD, nms=NMS_IOU
     with torch.inference_mode():
         for batch in loader:
             dev = anchors.device
-            cls, box, it = model(batch["lidar_bev"].to(dev, non_blocking=True),
-                                 batch["map_bev"].to(dev, non_blocking=True))
+            lidar, mp = batch["lidar_bev"].to(dev, non_blocking=True), batch["map_bev"].to(dev, non_blocking=True)
+            cls, box, it = model(lidar, mp)
             gts.append(batch["gt_list"])
+            if attn_dump is not None:
+                held.append((lidar, mp))
             prev = pipe.push(cls, box, it)
             if prev is not None:
                 emit(prev)
@@ -117,6 +167,8 @@ def main_eval_vit(argv=None, variant="vit"):
     """variant "vit" (eval_vit.py) or "cnn" (eval_cnn.py: IntentNetCNN, stride 8)."""
     args = parse_args(argv)
     tag = "ViT" if variant == "vit" else "CNN"
+    if args.attn_maps is not None and variant != "vit":
+        raise SystemExit("--attn-maps: IntentNetCNN has no attention to map (use eval_vit.py)")
     if args.checkpoint is None:
         args.checkpoint = MODEL_SAVE_PATH_VIT if variant == "vit" else MODEL_SAVE_PATH_CNN
     if not torch.cuda.is_available():
@@ -180,8 +232,13 @@ def main_eval_vit(argv=None, variant="vit"):
     print(f"Anchors for {tag} evaluation generated (stride {stride}), shape: {tuple(anchors.shape)}")
 
     t0 = time.perf_counter()
-    results = run_inference(model, loader, anchors, rotated_nms=args.rotated_nms)
+    dump = None
+    if args.attn_maps is not None:
+        dump = AttnDump(args.attn_maps, args.attn_top, [int(b) for b in args.attn_blocks.split(",") if b.strip()])
+    results = run_inference(model, loader, anchors, rotated_nms=args.rotated_nms, attn_dump=dump)
     torch.cuda.synchronize()
+    if dump is not None:
+        print(f"Attention maps of {dump.written} batches written to {dump.out_dir}")
     dt = time.perf_counter() - t0
     print(f"Collected results for {len(results)} samples ({len(results) / dt:.2f} samples/s incl. host transfer)")
 

@@ -306,6 +306,37 @@ class IntentNetViT(nn.Module):
             m.compute_dtype = dtype
         return self
 
+    def attention_maps(self, lidar_bev, map_bev, sample, centers_xy_m, blocks=(-1,), head_mean=True):
+        """Where the two streams looked for given detections: the attention probabilities of the
+        query token under each box centre, at the chosen ViT blocks, as BEV heat maps.
+
+        ``sample`` [R]: the batch index of each query; ``centers_xy_m`` [R, 2]: ego-metric box centres
+        (columns 0, 1 of ``pred_boxes_xywha``). Each stream maps a centre to its own patch cell
+        (utils.bev_cells: a patch-16 map stream has a coarser grid and its own cells) and queries
+        token 1 + gy * Wf + gx through VisionTransformer.attention_rows. Returns a dict of f32 tensors,
+        L = len(blocks), the H axis only without ``head_mean``:
+          "lidar", "map"              [L, R, (H,) Hf, Wf]  the probabilities over the patch tokens
+          "lidar_cls", "map_cls"      [L, R, (H)]          the mass on the CLS token
+          "lidar_cells", "map_cells"  [R, 2]               the queried (gy, gx) cell (int64)
+        Every plane plus its CLS mass sums to 1. Eval semantics under no_grad; the model's mode,
+        weights and DropPath state are untouched (attention_rows)."""
+        from utils import bev_cells
+        bb = self.backbone
+        sample = torch.as_tensor(sample).reshape(-1).long().cpu()
+        centers = torch.as_tensor(centers_xy_m).detach().reshape(-1, 2).float().cpu()
+        if sample.numel() != centers.shape[0]:
+            raise ValueError(f"attention_maps: {sample.numel()} samples for {centers.shape[0]} centres")
+        out = {}
+        for name, vit, x in (("lidar", bb.vit_lidar, lidar_bev), ("map", bb.vit_map, map_bev)):
+            Hf, Wf = vit.patch_embed.grid_size
+            cells = bev_cells(centers, (Hf, Wf), vit.patch_embed.patch_size[0])
+            token = vit.num_prefix_tokens + cells[:, 0] * Wf + cells[:, 1]
+            rows = vit.attention_rows(x, sample, token, blocks=blocks, head_mean=head_mean)
+            out[name] = rows[..., vit.num_prefix_tokens:].reshape(*rows.shape[:-1], Hf, Wf)
+            out[name + "_cls"] = rows[..., 0]
+            out[name + "_cells"] = cells
+        return out
+
     def _neck_meta(self, B):
         bb = self.backbone
         names = bb.neck_names() + ["det_head.conv.weight", "det_head.conv.bias", "intention_head.conv.weight",

@@ -433,6 +433,57 @@ def attn_bwd(qkv, out, dout, lse, B, N, H, cdt):
     return dqkv
 
 
+def _request_index(v, hi, what):
+    """A host list or a tensor of request indices -> a checked host int64 tensor (ValueError outside
+    [0, hi): a bad index never reaches the device)."""
+    v = torch.as_tensor(v).detach().reshape(-1).cpu()
+    if v.numel() == 0:
+        return v.long()
+    if v.is_floating_point() or v.dtype == torch.bool:
+        raise ValueError(f"attn_rows: {what} indices must be integers, got {v.dtype}")
+    v = v.long()
+    if v.numel() and (int(v.min()) < 0 or int(v.max()) >= hi):
+        raise ValueError(f"attn_rows: {what} index out of range [0, {hi}): min {int(v.min())}, max {int(v.max())}")
+    return v
+
+
+class RowRequests:
+    """Checked attention-row requests on the device: ``idx`` int32 [2, R] (samples; tokens), valid for
+    a [B, N] token grid. Built once (host range check + one upload) and passed to attn_rows as
+    ``sample`` for every block of a stream, so the per-block calls neither check nor upload again."""
+    __slots__ = ("B", "N", "idx")
+
+    def __init__(self, sample, token, B, N, device):
+        s, t = _request_index(sample, B, "sample"), _request_index(token, N, "token")
+        if s.numel() != t.numel():
+            raise ValueError(f"attn_rows: {s.numel()} samples for {t.numel()} tokens")
+        self.B, self.N = int(B), int(N)
+        self.idx = torch.stack([s, t]).to(torch.int32).to(device)
+
+
+def attn_rows(qkv, B, N, H, cdt, sample, token=None, head_mean=False, prescaled=False):
+    """Attention probabilities of the query rows (sample[r], token[r]) (ivit_attn_rows): qkv
+    [B*N, 3*H*64] as attn_fwd / attn_fwd_q2 take it (``prescaled``: the bf16 Q block of qkv_fwd_q2 /
+    panel_fwd(qcols=...)) -> f32 [R, H, N], or [R, N] with ``head_mean`` (the mean over the heads).
+    ``sample`` / ``token``: host lists or tensors, range-checked here (ValueError) and uploaded as
+    int32 — or ``sample`` a RowRequests that already is (``token`` None)."""
+    if dt(qkv) != cdt or not qkv.is_contiguous() or qkv.numel() != B * N * 3 * H * 64:
+        raise ValueError(f"attn_rows: qkv {tuple(qkv.shape)} {qkv.dtype} is not a contiguous [B*N, 3*H*64] tensor of "
+                         f"the compute dtype (B={B}, N={N}, H={H})")
+    if prescaled and cdt != BF16:
+        raise ValueError("attn_rows: prescaled Q exists on the bf16 path only")
+    req = sample if isinstance(sample, RowRequests) else RowRequests(sample, token, B, N, qkv.device)
+    if (req.B, req.N) != (B, N) or req.idx.device != qkv.device:
+        raise ValueError(f"attn_rows: requests checked for B={req.B}, N={req.N} on {req.idx.device}")
+    R = req.idx.shape[1]
+    out = torch.empty((R, N) if head_mean else (R, H, N), dtype=torch.float32, device=qkv.device)
+    if R == 0:
+        return out
+    lib.ivit_attn_rows(cdt, ptr(qkv), B, N, H, 64, int(bool(prescaled)), ptr(req.idx[0]), ptr(req.idx[1]), R,
+                       int(bool(head_mean)), ptr(out), stream())
+    return out
+
+
 def add_act_grad(a, b=None, pre=None, row_scale=None, row_elems=1, out_dtype=None):
     out = torch.empty(a.shape, dtype=out_dtype or a.dtype, device=a.device)
     lib.ivit_add_act_grad(ptr(a), dt(a), ptr(b), dt(b) if b is not None else F32, ptr(pre),

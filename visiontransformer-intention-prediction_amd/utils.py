@@ -38,6 +38,22 @@ def generate_anchors(bev_height: int = GRID_HEIGHT_PX, bev_width: int = GRID_WID
     return out
 
 
+def bev_cells(centers_xy_m: torch.Tensor, grid_size, patch: int, voxel_size: float = VOXEL_SIZE_M,
+              offset_x_px: float = BEV_PIXEL_OFFSET_X, offset_y_px: float = BEV_PIXEL_OFFSET_Y) -> torch.Tensor:
+    """Ego-metric box centres [R, 2] (x forward, y left: columns 0, 1 of a decoded box) -> the
+    (gy, gx) cell [R, 2] (int64) of a ``grid_size`` = (Hf, Wf) patch grid with ``patch`` pixels per
+    cell that contains them: the inverse of generate_anchors' centre formula (px = y / voxel +
+    offset_x, py = offset_y - x / voxel, cell = floor(p / patch)), clamped to the grid. Pure torch,
+    on the tensor's own device. The ViT token of a cell is 1 + gy * Wf + gx (token 0 is CLS)."""
+    c = torch.as_tensor(centers_xy_m).reshape(-1, 2).double()
+    Hf, Wf = int(grid_size[0]), int(grid_size[1])
+    px = c[:, 1] / voxel_size + offset_x_px
+    py = offset_y_px - c[:, 0] / voxel_size
+    gx = torch.floor(px / patch).clamp(0, Wf - 1).long()
+    gy = torch.floor(py / patch).clamp(0, Hf - 1).long()
+    return torch.stack([gy, gx], dim=1)
+
+
 def compute_axis_aligned_iou(boxes1_xywh: torch.Tensor, boxes2_xywh: torch.Tensor) -> torch.Tensor:
     """utils.py:276-292 (uses columns 0..3)."""
     b1, b2 = _as5(boxes1_xywh), _as5(boxes2_xywh)

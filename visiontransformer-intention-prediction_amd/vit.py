@@ -196,6 +196,67 @@ class VisionTransformer(nn.Module):
             yield
         return t
 
+    def attention_rows(self, x, sample, token, blocks=None, head_mean=True):
+        """The attention probabilities of the query tokens (sample[r], token[r]) at the chosen blocks
+        (what a forward hook on timm's ``Attention`` reads off softmax(q k^T / sqrt(d))): f32
+        [len(blocks), R, N], or [len(blocks), R, H, N] without the head mean; N = patches + 1, key 0
+        is CLS. ``blocks``: indices into ``self.blocks`` (negative from the end), default all; the
+        result follows their order.
+
+        Eval semantics (no DropPath) under ``torch.no_grad()`` whatever ``self.training`` is; the
+        blocks' ``training`` / ``last_scales`` are put back. The fused block ops keep their qkv to
+        themselves, so before a requested block this recomputes norm1 and the qkv projection of the
+        block's input with the ops the block itself uses (one extra LayerNorm + GEMM per requested
+        block; on the row-panel path the LayerNorm is the previous block's hand-over), then
+        ops.attn_rows; the residual stream advances through the block's own forward_flat."""
+        depth = len(self.blocks)
+        blocks = list(range(depth)) if blocks is None else [int(b) for b in blocks]
+        want = [b + depth if b < 0 else b for b in blocks]
+        if any(b < 0 or b >= depth for b in want):
+            raise ValueError(f"attention_rows: blocks {blocks} outside a depth-{depth} stream")
+        B, C, H, W = x.shape
+        if (H, W) != self.patch_embed.img_size:
+            raise ValueError(f"Input size {(H, W)} != model img_size {self.patch_embed.img_size} (timm strict size)")
+        cdt = self._cdt()
+        cd = torch.bfloat16 if cdt == BF16 else torch.float32
+        nh = self.blocks[0].attn.num_heads
+        N = self.patch_embed.num_patches + 1
+        fuse = ops.block_on_panel(cdt, self.embed_dim)
+        req = ops.RowRequests(sample, token, B, N, x.device)  # checked and uploaded once for all blocks
+        found = {}
+        saved = [(blk.training, blk.last_scales) for blk in self.blocks]
+        try:
+            for blk in self.blocks:
+                blk.training = False  # Block._scales: identity DropPath, draws nothing
+            with torch.no_grad():
+                pe = (x.float().contiguous(), self.patch_embed.proj.weight, self.patch_embed.proj.bias,
+                      self.pos_embed, self.cls_token, cdt)
+                p8 = self.patch_embed.proj.weight.shape[-1] == 8
+                t = ops.PatchEmbedFn.apply(*pe, None) if p8 else ops.PatchEmbedGenericFn.apply(*pe)
+                ln = None
+                for i, blk in enumerate(self.blocks[:max(want) + 1]):
+                    if i in want:
+                        ln1 = ln[0] if ln is not None else ops.layernorm_fwd(t, blk.norm1.weight, blk.norm1.bias,
+                                                                             1e-6, cd)[0]
+                        qw, qb = blk.attn.qkv.weight, blk.attn.qkv.bias
+                        if fuse:
+                            qkv = ops.panel_fwd(ln1, qw, qb, qcols=nh * 64, qscale=ops.Q2_SCALE)[0]
+                        elif cdt == BF16:
+                            qkv = ops.qkv_fwd_q2(ln1, ops.cast_weight(qw, cd), qb, nh * 64)
+                        else:
+                            qkv = ops.linear_fwd(ln1, qw, qb, cdt)[0]
+                        found[i] = ops.attn_rows(qkv, B, N, nh, cdt, req, head_mean=head_mean, prescaled=cdt == BF16)
+                        del qkv
+                    if i == max(want):
+                        break  # nothing reads the residual stream past the last requested block
+                    nxt = self.blocks[i + 1].norm1 if fuse else None
+                    t, nxt_ln = blk.forward_flat(t, B, N, cdt, ln_in=ln, next_norm=nxt)
+                    ln = nxt_ln if nxt is not None else None
+        finally:
+            for blk, (tr, ls) in zip(self.blocks, saved):
+                blk.training, blk.last_scales = tr, ls
+        return torch.stack([found[b] for b in want])
+
     def forward_features(self, x):
         B = x.shape[0]
         t = self.forward_tokens(x)
