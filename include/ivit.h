@@ -415,7 +415,10 @@ int ivit_nms_batched(const float* boxes_xywha, const float* scores, const long* 
  * out_scores [B, NA], out_boxes [B, NA, 5] (decoded xywha) and out_intent [B, NA] (int64);
  * out_count [B] int64 is the one value the caller reads back. Scores are torch's f32 GPU sigmoid,
  * boxes ivit_decode_boxes', keep order torchvision CPU nms's (bit-exact).
- * work >= ivit_eval_post_workspace(B, NA) bytes.                                               */
+ * work >= ivit_eval_post_workspace(B, NA) bytes: 76 B per row (B * NA rows) for the compacted
+ * scores, anchors, boxes, sort scratch, order, corners and keep list, plus the suppression mask,
+ * which is reserved for the worst case (every anchor of every sample passes) and dominates:
+ * B * NA * ceil(NA / 64) * 8 bytes, about 2.0 GB at B = 32, NA = 22 500.                        */
 long ivit_eval_post_workspace(long B, long NA);
 int ivit_eval_post(const float* cls, const float* box_rel, const float* intent, const float* anchors, long B, long NA,
                    long K, float conf_thr, double iou_thr, float* out_scores, float* out_boxes, long* out_intent,

@@ -51,6 +51,45 @@ def test_workspace_queries_are_pure_host():
     assert dll.ivit_eval_post_rotated_workspace(32, 22500) >= 32 * 22500 * 352 * 8
 
 
+def _al16(x):
+    return (x + 15) // 16 * 16
+
+
+def test_workspace_values_are_the_documented_formulas():
+    """The batched and eval workspace queries, value for value (callers size their buffers with
+    them; the layouts behind them may be reorganised, the numbers may not move)."""
+    dll = _lib.lib.load()
+    for ns in ([1], [64], [10, 65, 65], [22500]):  # (S, T, W) = (1, 1, 1), (1, 64, 64), (3, 140, 270), ...
+        S, T = len(ns), sum(ns)
+        W = sum(n * ((n + 63) // 64) for n in ns)
+        axis = _al16(4 * T) + _al16(20 * T) + _al16(8 * W) + 4 * _al16(4 * T) + 64
+        assert dll.ivit_nms_batched_workspace(S, T, W) == axis, ns
+        assert dll.ivit_nms_rotated_batched_workspace(S, T, W) == axis + _al16(80 * T) + _al16(32 * T), ns
+    for B, NA in ((1, 1), (2, 64), (8, 22500)):
+        R, nw = B * NA, (NA + 63) // 64
+        sizes = [4 * B, 4 * R, 4 * R, 20 * R, 4 * R, 4 * R, 4 * R, 4 * R, 4 * R, 20 * R, 8 * R, 8 * R * nw]
+        axis = sum(_al16(s) for s in sizes) + 16
+        assert dll.ivit_eval_post_workspace(B, NA) == axis, (B, NA)
+        assert dll.ivit_eval_post_rotated_workspace(B, NA) == axis + _al16(80 * R) + _al16(32 * R), (B, NA)
+    for fn in (dll.ivit_nms_batched_workspace, dll.ivit_nms_rotated_batched_workspace):
+        assert fn(0, 0, 0) == fn(3, 0, 0) == fn(0, 5, 5) == 64
+    for fn in (dll.ivit_eval_post_workspace, dll.ivit_eval_post_rotated_workspace):
+        assert fn(0, 64) == fn(4, 0) == 64
+
+
+def test_argument_validation_names_the_axis_entries_too():
+    dll = _lib.lib.load()
+    rc = dll.ivit_nms_batched(None, None, None, None, 1, 131073, 131073, 131073 * 2049, 0.2, None, None, None, 1 << 62,
+                              None)
+    assert rc < 0 and dll.ivit_last_error().startswith(b"ivit_nms_batched: n=131073")
+    rc = dll.ivit_nms(None, None, 131073, 0.2, None, None, None, 1 << 62, None)
+    assert rc < 0 and dll.ivit_last_error().startswith(b"ivit_nms: n=131073")
+    rc = dll.ivit_eval_post(None, None, None, None, 1, 64, 0, 0.1, 0.2, None, None, None, None, None, 1 << 62, None)
+    assert rc < 0 and dll.ivit_last_error().startswith(b"ivit_eval_post: bad sizes") and b"K 0" in dll.ivit_last_error()
+    rc = dll.ivit_nms_batched(None, None, None, None, 1, 64, 64, 64, 0.2, None, None, None, 64, None)
+    assert rc < 0 and dll.ivit_last_error() == b"ivit_nms_batched: workspace too small"
+
+
 def test_argument_validation_without_device():
     dll = _lib.lib.load()
     rc = dll.ivit_nms_rotated_batched(None, None, None, None, 1, 131073, 131073, 131073 * 2049, 0.2, None, None, None,

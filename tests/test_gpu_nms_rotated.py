@@ -271,6 +271,37 @@ def test_postprocess_batch_rotated_nms():
         assert ga.shape != aa.shape or not torch.equal(ga, aa)  # and changes the outcome
 
 
+@pytest.mark.parametrize("rotated", [False, True])
+def test_postprocess_batch_leading_sample_with_nothing_passing(rotated):
+    """NA = 130 (three mask words, the last one partial); samples 0 and 2 have no row above the
+    confidence threshold, so the walk of the FIRST sample starts at the front of its buffers."""
+    import utils
+    from test_gpu_entry import _post_reference
+    g = torch.Generator().manual_seed(8)
+    B, NA, K = 3, 130, 8
+    anchors = O.generate_anchors(64, 96, 8)[:NA]
+    cls = torch.randn(B, NA, 1, generator=g) * 2.0
+    cls[0] = -20.0
+    cls[2] = -20.0
+    box = torch.randn(B, NA, 6, generator=g) * 0.3
+    it = torch.randn(B, NA, K, generator=g)
+    dev_args = (cls.cuda(), box.cuda(), it.cuda(), anchors.cuda())
+    want = (_post_reference_rotated if rotated else _post_reference)(*dev_args)
+    passing = int((torch.sigmoid(dev_args[0][1].reshape(-1)) >= 0.1).sum())
+    assert 1 <= want[1][0].numel() < passing  # the reference keeps a box and suppresses one
+    got = utils.postprocess_batch(*dev_args, 0.1, THR, rotated_nms=rotated)
+    assert len(got) == B
+    for b, (p, (ws, wb, wi)) in enumerate(zip(got, want)):
+        assert p["pred_scores"].dtype == torch.float32 and p["pred_boxes_xywha"].dtype == torch.float32
+        assert p["pred_intentions"].dtype == torch.int64
+        assert torch.equal(p["pred_scores"].cpu(), ws), b
+        assert torch.equal(p["pred_boxes_xywha"].cpu(), wb), b
+        assert torch.equal(p["pred_intentions"].cpu(), wi), b
+    for b in (0, 2):
+        assert got[b]["pred_scores"].shape == (0,) and got[b]["pred_boxes_xywha"].shape == (0, 5)
+        assert got[b]["pred_intentions"].shape == (0,)
+
+
 def test_post_pipeline_rotated_equals_per_batch_postprocess():
     import utils
     g = torch.Generator().manual_seed(6)

@@ -988,6 +988,53 @@ def test_nms_random_vs_oracle(thr):
         assert np.array_equal(k.cpu().numpy(), w), i
 
 
+def _nms_family(n, g):
+    """n axis-aligned boxes in a 10 x 10 square, sides in [0.5, 2.5], scores in eighths (mass ties)."""
+    b = torch.stack([10 * torch.rand(n, generator=g), 10 * torch.rand(n, generator=g),
+                     0.5 + 2 * torch.rand(n, generator=g), 0.5 + 2 * torch.rand(n, generator=g), torch.zeros(n)], 1)
+    return b, torch.round(torch.rand(n, generator=g) * 8) / 8
+
+
+def test_nms_batched_empty_segments():
+    """A leading and an inner empty segment on the axis path: the scan settles n = 0 before it
+    reads anything (the leading one's rows would lie in front of the workspace)."""
+    from oracle import ivit_oracle as O
+    import utils
+    g = torch.Generator().manual_seed(31)
+    b10, s10 = _nms_family(10, g)
+    b65, s65 = _nms_family(65, g)
+    e, es = torch.zeros((0, 5)), torch.zeros((0,))
+    parts = [(e, es), (b10, s10), (e, es), (b65, s65)]
+    want = [np.zeros((0,), np.int64)] + [O.nms_numpy(b.numpy(), s.numpy(), 0.2) for b, s in parts[1:]]
+    assert [len(w) for w in want][0::2] == [0, 0] and 0 < len(want[1]) and 0 < len(want[3]) < 65
+    got = utils.nms_batched([b.to(DEV) for b, _ in parts], [s.to(DEV) for _, s in parts], 0.2)
+    assert len(got) == 4
+    for k, w in zip(got, want):
+        assert k.dtype == torch.int64 and k.is_cuda
+        assert np.array_equal(k.cpu().numpy(), w)
+    assert [k.numel() for k in got][0::2] == [0, 0] and 0 < got[1].numel() and 0 < got[3].numel() < 65
+    out = utils.apply_nms(e.to(DEV), es.to(DEV), 0.2)
+    assert out.numel() == 0 and out.dtype == torch.int64 and out.is_cuda
+
+
+@pytest.mark.parametrize("thr", [0.2, 0.0])
+def test_nms_single_sample_equals_batch_of_one(thr):
+    """ivit_nms is the batched pipeline with one sample: the same keep list, and the oracle's, at
+    one box, a full mask word, one box more and a partial third word."""
+    from oracle import ivit_oracle as O
+    import utils
+    g = torch.Generator().manual_seed(41)
+    for n in (1, 64, 65, 129):
+        b, s = _nms_family(n, g)
+        ref = O.nms_numpy(b.numpy(), s.numpy(), thr)
+        single = utils.apply_nms(b.to(DEV), s.to(DEV), thr)
+        batched = utils.nms_batched([b.to(DEV)], [s.to(DEV)], thr)[0]
+        assert single.dtype == batched.dtype == torch.int64
+        assert np.array_equal(single.cpu().numpy(), ref), n
+        assert np.array_equal(batched.cpu().numpy(), ref), n
+        assert n == 1 or 0 < len(ref) < n, n
+
+
 def test_nms_past_the_held_words_and_many_kept_per_column():
     """n = 26 000 (407 mask words: the scan's later-word update past its two held words per thread)
     with dense overlaps and scores in descending blocks, so columns keep more than 8 boxes (the

@@ -6,6 +6,7 @@
 * n = 4096 boxes: the only route to rotated NMS without the kernel, compute_rotated_iou n x n
   + the matrix read back + the greedy walk on the host, against apply_nms(rotated=True); the two
   keep lists are compared;
+* utils.nms_device (ivit_nms, the single-sample axis path) at n = 64, 4096 and 22 500;
 * the share of lanes that have a pair in the exact phase of the mask kernel, computed from the
   prefilter's definition (pairs per workgroup of 64 rows x 512 columns, 64 pairs per wave step),
   not from hardware counters.
@@ -204,6 +205,13 @@ def main():
                     "apply_nms_axis_ms": round(a_ms, 3), "speedup_over_matrix_route": round(m_ms / k_ms, 1),
                     "keeps_equal": bool(np.array_equal(want, got)), "kept": int(got.shape[0]),
                     **lane_share(b[torch.sort(s, descending=True, stable=True)[1]])}
+    # the single-sample axis path (ivit_nms) without its count read: enqueue + device time per call
+    out["nms_device"] = []
+    for n in (64, 4096, 22500):
+        b, s = family(n, 3)
+        ms, calls = timed(lambda: utils.nms_device(b, s, THR), max_it=2000)
+        out["nms_device"].append({"n": n, "ms": round(ms, 4), "calls": calls})
+    print(json.dumps(out["nms_device"]), flush=True)
     if not args.no_eval_loop:
         # alternating, axis first and last: the spread between the two axis runs is the noise
         loop = {}

@@ -54,39 +54,7 @@ __global__ void decode_kernel(const float* rel, const float* anchors, const long
 
 // ---- NMS (torchvision CPU nms_kernel_impl): stable descending sort; f32 corners/areas/IoU;
 //      suppress j if (double)IoU > thr.
-// rank by counting: rank(i) = #{j : s_j > s_i  or  (s_j == s_i and j < i)}
-__global__ void nms_rank_kernel(const float* __restrict__ s, long n, int* __restrict__ order) {
-  __shared__ float tile[256];
-  const long i = (long)blockIdx.x * 256 + threadIdx.x;
-  const float si = i < n ? s[i] : 0.f;
-  long rank = 0;
-  for (long j0 = 0; j0 < n; j0 += 256) {
-    __syncthreads();
-    if (j0 + threadIdx.x < n) tile[threadIdx.x] = s[j0 + threadIdx.x];
-    __syncthreads();
-    const int lim = (int)min((long)256, n - j0);
-    for (int k = 0; k < lim; ++k) {
-      const float sj = tile[k];
-      const long j = j0 + k;
-      rank += (sj > si) || (sj == si && j < i);
-    }
-  }
-  if (i < n) order[rank] = (int)i;
-}
-
-__global__ void nms_sorted_boxes_kernel(const float* __restrict__ b, const int* __restrict__ order, long n,
-                                        float* __restrict__ sb) {
-  const long p = (long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (p >= n) return;
-  const float* q = b + (long)order[p] * 5;
-  const float x1 = q[0] - q[2] / 2.f, y1 = q[1] - q[3] / 2.f, x2 = q[0] + q[2] / 2.f, y2 = q[1] + q[3] / 2.f;
-  sb[p * 5 + 0] = x1;
-  sb[p * 5 + 1] = y1;
-  sb[p * 5 + 2] = x2;
-  sb[p * 5 + 3] = y2;
-  sb[p * 5 + 4] = (x2 - x1) * (y2 - y1);
-}
-
+//
 // torchvision's test, bit for bit: (double)RN32(inter / u) > thr with u = (area_i + area_j) - inter in
 // f32, i.e. RN32(inter / u) >= t, t the smallest float whose double exceeds thr. The IEEE division is
 // a ~10-instruction VALU sequence, and with divergent lanes the whole wave waits for it (anchors
@@ -199,15 +167,6 @@ IVIT_DEV void nms_mask_body(const float* __restrict__ sb, long n, int nw, const 
   }
 }
 
-// mask[p][w] bit k: sorted box 64w+k (> p) overlaps sorted box p with IoU > thr.
-// grid (ceil(nw / NMS_CB), nw)
-__global__ __launch_bounds__(64) void nms_mask_kernel(const float* __restrict__ sb, long n, int nw, NmsThr th,
-                                                      unsigned long long* __restrict__ mask) {
-  const int cb0 = blockIdx.x * NMS_CB, rb = blockIdx.y;
-  if (cb0 + NMS_CB <= rb) return;
-  nms_mask_body(sb, n, nw, th, mask, rb, cb0);
-}
-
 constexpr int NMS_MAXW = 2048;  // n <= 131072
 
 // The greedy walk of torchvision's nms over the suppression mask, one workgroup per sample. Column
@@ -229,6 +188,10 @@ IVIT_DEV void nms_scan_body(const unsigned long long* __restrict__ mask, long n,
   __shared__ unsigned long long kept_s[3];
   __shared__ long cnt_s;
   __shared__ int kbit[3][64];
+  if (n <= 0) {  // an empty sample, settled before ld_row clamps a row index to n - 1 = -1
+    if (threadIdx.x == 0) *count_out = 0;
+    return;
+  }
   for (int w = threadIdx.x; w < nw; w += 256) removed[w] = 0ull;
   if (threadIdx.x == 0) cnt_s = 0;
   __syncthreads();
@@ -341,23 +304,19 @@ IVIT_DEV void nms_scan_body(const unsigned long long* __restrict__ mask, long n,
   if (threadIdx.x == 0) *count_out = cnt_s;
 }
 
-__global__ __launch_bounds__(256) void nms_scan_kernel(const unsigned long long* __restrict__ mask, long n, int nw,
-                                                       const int* __restrict__ order, long* __restrict__ keep,
-                                                       long* __restrict__ count) {
-  nms_scan_body(mask, n, nw, order, keep, count);
-}
-
-// ---- batched NMS and the fused eval post-processing -------------------------------------------
+// ---- the NMS pipeline (sort, suppression mask, greedy walk) over a batch of samples, and the
+// fused eval post-processing ---------------------------------------------------------------------
 // Sample s owns rows lo(s) .. lo(s) + n(s) - 1 of every per-row array and the mask words mo(s) ..:
-// either host prefix offsets (seg [S+1], mask_off [S]: ivit_nms_batched) or a fixed capacity per
-// sample with the row counts on the device (ivit_eval_post: nothing is read back before the NMS).
+// host prefix offsets (seg [S+1], mask_off [S]: ivit_nms_batched), or a fixed capacity per sample
+// with the row counts on the device (ivit_eval_post: nothing is read back before the NMS), or
+// with every sample full (ivit_nms: one sample of row_stride rows, known on the host).
 struct SegView {
   const long* seg;   // [S+1] row offsets, or null
   const long* moff;  // [S] mask word offsets (with seg)
-  const int* cnt;    // [S] rows per sample (without seg)
+  const int* cnt;    // [S] rows per sample (without seg); null: row_stride rows in every sample
   long row_stride, mask_stride;
   IVIT_DEV long lo(int s) const { return seg ? seg[s] : (long)s * row_stride; }
-  IVIT_DEV long n(int s) const { return seg ? seg[s + 1] - seg[s] : (long)cnt[s]; }
+  IVIT_DEV long n(int s) const { return seg ? seg[s + 1] - seg[s] : cnt ? (long)cnt[s] : row_stride; }
   IVIT_DEV long mo(int s) const { return seg ? moff[s] : (long)s * mask_stride; }
 };
 
@@ -506,6 +465,35 @@ IVIT_DEV void sorted_corners(const float* q, float* d) {
   d[4] = (x2 - x1) * (y2 - y1);
 }
 
+// ivit_nms, stage 1: the same order by counting, rank(i) = #{j : s_j > s_i or (s_j == s_i and
+// j < i)} (== on floats: -0 ties with +0), then the sorted corner boxes. O(n^2) spread over
+// n / 256 workgroups: at n = 64 the call takes 28 us against 41 us through the one-workgroup
+// radix sort below (profiles/nms_unify_bench.json), and small n is what a single call is for.
+__global__ void nms_rank_kernel(const float* __restrict__ s, long n, int* __restrict__ order) {
+  __shared__ float tile[256];
+  const long i = (long)blockIdx.x * 256 + threadIdx.x;
+  const float si = i < n ? s[i] : 0.f;
+  long rank = 0;
+  for (long j0 = 0; j0 < n; j0 += 256) {
+    __syncthreads();
+    if (j0 + threadIdx.x < n) tile[threadIdx.x] = s[j0 + threadIdx.x];
+    __syncthreads();
+    const int lim = (int)min((long)256, n - j0);
+    for (int k = 0; k < lim; ++k) {
+      const float sj = tile[k];
+      const long j = j0 + k;
+      rank += (sj > si) || (sj == si && j < i);
+    }
+  }
+  if (i < n) order[rank] = (int)i;
+}
+
+__global__ void nms_sorted_boxes_kernel(const float* __restrict__ b, const int* __restrict__ order, long n,
+                                        float* __restrict__ sb) {
+  const long p = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (p < n) sorted_corners(b + (long)order[p] * 5, sb + p * 5);
+}
+
 // ivit_nms_batched, stage 1: one workgroup per sample — keys from the scores, the stable
 // descending sort, the sorted corner boxes. k0/v0/k1/v1: [total] scratch.
 __global__ __launch_bounds__(PS_T) void nms_sort_b_kernel(const float* __restrict__ b, const float* __restrict__ scores,
@@ -532,6 +520,7 @@ __global__ __launch_bounds__(PS_T) void nms_sort_b_kernel(const float* __restric
   }
 }
 
+// mask[p][w] bit k: sorted box 64w+k (> p) overlaps sorted box p with IoU > thr.
 // grid (ceil(nwmax / NMS_CB), nwmax, samples)
 __global__ __launch_bounds__(64) void nms_mask_b_kernel(const float* __restrict__ sb_all, SegView sv, NmsThr th,
                                                         unsigned long long* __restrict__ mask_all) {
@@ -543,6 +532,7 @@ __global__ __launch_bounds__(64) void nms_mask_b_kernel(const float* __restrict_
   nms_mask_body(sb_all + o * 5, n, nw, th, mask_all + sv.mo(sm), rb, cb0);
 }
 
+// grid (samples)
 __global__ __launch_bounds__(256) void nms_scan_b_kernel(const unsigned long long* __restrict__ mask_all, SegView sv,
                                                          const int* __restrict__ order_all,
                                                          long* __restrict__ keep_all, long* __restrict__ count) {
@@ -734,19 +724,6 @@ __global__ __launch_bounds__(64) void nms_rot_mask_b_kernel(const double* __rest
   nms_rot_mask_body(rp_all + o * 10, rc_all + 2 * o, n, nw, thr, pre, mask_all + sv.mo(sm), rb, cb0);
 }
 
-// nms_scan_body loads rows 0 and 1 before it looks at n: an empty sample is settled here
-__global__ __launch_bounds__(256) void nms_rot_scan_b_kernel(const unsigned long long* __restrict__ mask_all,
-                                                             SegView sv, const int* __restrict__ order_all,
-                                                             long* __restrict__ keep_all, long* __restrict__ count) {
-  const int sm = blockIdx.x;
-  const long o = sv.lo(sm), n = sv.n(sm);
-  if (n <= 0) {
-    if (threadIdx.x == 0) count[sm] = 0;
-    return;
-  }
-  nms_scan_body(mask_all + sv.mo(sm), n, (int)((n + 63) / 64), order_all + o, keep_all + o, count + sm);
-}
-
 // ---- eval post-processing (eval_vit.py:156-176) for a whole batch, capacity NA rows per sample.
 struct PostWs {
   int* n;            // [S] rows passing the confidence threshold
@@ -759,6 +736,8 @@ struct PostWs {
   float* sb;         // [S*NA*5] sorted corners + area
   long* keep;        // [S*NA] kept compacted-row indices in score order
   unsigned long long* mask;
+  double* rp;        // [S*NA*10] rotated only: nms_rot_prep_kernel's polygons
+  float4* rc;        // [S*NA*2]  and prefilter records
 };
 
 // torch's f32 sigmoid on the GPU: 1 / (1 + exp(-x)), IEEE division (UnarySpecialOpsKernel.cu)
@@ -886,6 +865,111 @@ extern "C" int ivit_decode_boxes(const float* rel, const float* anchors, const l
   return 0;
 }
 
+// ---- NMS entries. Every one of them runs sort -> suppression mask -> greedy walk; the five
+// entries differ in who sorts (nms_rank_kernel for one sample, nms_sort_b_kernel for a batch,
+// post_select_kernel after its selection), in the SegView, and in the suppression test.
+namespace {
+long al16(long b) { return (b + 15) / 16 * 16; }
+
+// IVIT_LAUNCH_CHECK for the shared implementations: the message names the entry that was called
+int launch_status(const char* name) {
+  const hipError_t e = hipGetLastError();
+  if (e != hipSuccess) ivit_set_error("%s: %s", name, hipGetErrorString(e));
+  return (int)e;
+}
+
+// The stages after the sort, for samples whose largest row count is max_n: [the rotated test's
+// per-box polygons and prefilter records ->] the suppression mask -> the greedy walk.
+// boxes: the unsorted xywha rows and rp / rc: the per-box records (rotated only); sb: the sorted
+// corner rows (axis only).
+void nms_mask_and_scan(const float* boxes, const int* order, const float* sb, double* rp, float4* rc,
+                       unsigned long long* mask, const SegView& sv, long samples, long max_n, double thr, bool rotated,
+                       long* keep, long* count, hipStream_t st) {
+  const int nwmax = (int)((max_n + 63) / 64);
+  const dim3 mask_grid(ivit_cdiv(nwmax, NMS_CB), nwmax, samples);
+  if (rotated) {
+    hipLaunchKernelGGL(nms_rot_prep_kernel, dim3(ivit_cdiv(max_n, 256), samples), dim3(256), 0, st, boxes, order, sv,
+                       rp, rc);
+    hipLaunchKernelGGL(nms_rot_mask_b_kernel, mask_grid, dim3(64), 0, st, rp, rc, sv, thr, thr >= 0.0 ? 1 : 0, mask);
+  } else {
+    hipLaunchKernelGGL(nms_mask_b_kernel, mask_grid, dim3(64), 0, st, sb, sv, nms_thr(thr), mask);
+  }
+  hipLaunchKernelGGL(nms_scan_b_kernel, dim3(samples), dim3(256), 0, st, mask, sv, order, keep, count);
+}
+
+// The workspace of ivit_nms_batched / ivit_nms_rotated_batched, regions in this order,
+// each rounded up to 16 bytes, after a base rounded up to 16 (bytes includes 64 of slack for it).
+// The rotated form appends the polygons (80 B per row) and the prefilter records (32 B per row);
+// its sort stage is the shared one and still writes the corner rows.
+struct BatchWs {
+  int* order;                // [total]
+  float* sb;                 // [total*5]
+  unsigned long long* mask;  // [mask_words]
+  unsigned *k0, *k1;         // [total] sort scratch
+  int *v0, *v1;
+  double* rp;                // [total*10], rotated only
+  float4* rc;                // [total*2], rotated only
+  long bytes;
+};
+BatchWs batch_ws(void* work, long total, long mask_words, bool rotated) {
+  const uintptr_t base = ((uintptr_t)work + 15) & ~(uintptr_t)15;
+  long off = 0;
+  auto take = [&](long bytes) {
+    void* p = (void*)(base + off);
+    off += al16(bytes);
+    return p;
+  };
+  BatchWs w{};
+  w.order = (int*)take(4 * total);
+  w.sb = (float*)take(20 * total);
+  w.mask = (unsigned long long*)take(8 * mask_words);
+  w.k0 = (unsigned*)take(4 * total);
+  w.k1 = (unsigned*)take(4 * total);
+  w.v0 = (int*)take(4 * total);
+  w.v1 = (int*)take(4 * total);
+  if (rotated) {
+    w.rp = (double*)take(80 * total);
+    w.rc = (float4*)take(32 * total);
+  }
+  w.bytes = off + 64;
+  return w;
+}
+long batch_ws_bytes(long n_samples, long total, long mask_words, bool rotated) {
+  if (n_samples <= 0 || total <= 0) return 64;
+  return batch_ws(nullptr, total, mask_words, rotated).bytes;
+}
+
+// Batched torchvision-CPU-exact NMS (eval_vit.py:170 per sample, all samples in one launch per
+// stage). keep[lo(s) ..] receives sample s's kept LOCAL indices in score order, count[s] their
+// number. The score order is a stable descending sort (nms_sort_b_kernel: one workgroup per
+// sample; ties keep the row order, as torch's stable sort). With rotated, sorted box p suppresses
+// a later q iff (double)rotated_iou(p, q) > iou_thr.
+int nms_batched_impl(const char* name, bool rotated, const float* boxes_xywha, const float* scores, const long* seg,
+                     const long* mask_off, long n_samples, long total, long max_n, long mask_words, double iou_thr,
+                     long* keep, long* count, void* work, long work_bytes, void* stream) {
+  IVIT_CHECK_ARG(max_n <= 64L * NMS_MAXW, "%s: n=%ld exceeds %d", name, max_n, 64 * NMS_MAXW);
+  IVIT_CHECK_ARG(n_samples < 65536 && total < (1L << 31), "%s: too many samples / rows (%ld, %ld)", name, n_samples,
+                 total);
+  IVIT_CHECK_ARG(work_bytes >= batch_ws_bytes(n_samples, total, mask_words, rotated), "%s: workspace too small", name);
+  hipStream_t st = ivit_stream(stream);
+  if (n_samples <= 0) return 0;
+  if (max_n <= 0 || total <= 0) {
+    (void)hipMemsetAsync(count, 0, sizeof(long) * n_samples, st);
+    return launch_status(name);
+  }
+  const BatchWs w = batch_ws(work, total, mask_words, rotated);
+  const SegView sv{seg, mask_off, nullptr, 0, 0};
+  hipLaunchKernelGGL(nms_sort_b_kernel, dim3(n_samples), dim3(PS_T), 0, st, boxes_xywha, scores, seg, w.k0, w.v0, w.k1,
+                     w.v1, w.order, w.sb);
+  nms_mask_and_scan(boxes_xywha, w.order, w.sb, w.rp, w.rc, w.mask, sv, n_samples, max_n, iou_thr, rotated, keep,
+                    count, st);
+  return launch_status(name);
+}
+}  // namespace
+
+// One sample of n rows, n known on the host: its own sort stage, which needs no scratch, then the
+// shared stages with a one-sample SegView. It uses the first three regions of BatchWs; their
+// rounding (base <= 15, order and sb <= 12 each) fits the 64 bytes of slack in its workspace.
 extern "C" long ivit_nms_workspace(long n) {
   const long nw = (n + 63) / 64;
   return n * 4 + n * 5 * 4 + n * nw * 8 + 64;
@@ -901,245 +985,128 @@ extern "C" int ivit_nms(const float* boxes_xywha, const float* scores, long n, d
     IVIT_LAUNCH_CHECK();
     return 0;
   }
-  const int nw = (int)((n + 63) / 64);
-  char* w = (char*)work;
-  int* order = (int*)w;
-  w += (n * 4 + 15) / 16 * 16;
-  float* sb = (float*)w;
-  w += (n * 20 + 15) / 16 * 16;
-  unsigned long long* mask = (unsigned long long*)w;
-  hipLaunchKernelGGL(nms_rank_kernel, dim3(ivit_cdiv(n, 256)), dim3(256), 0, st, scores, n, order);
-  hipLaunchKernelGGL(nms_sorted_boxes_kernel, dim3(ivit_cdiv(n, 256)), dim3(256), 0, st, boxes_xywha, order, n, sb);
-  hipLaunchKernelGGL(nms_mask_kernel, dim3(ivit_cdiv(nw, NMS_CB), nw), dim3(64), 0, st, sb, n, nw, nms_thr(iou_thr),
-                     mask);
-  hipLaunchKernelGGL(nms_scan_kernel, dim3(1), dim3(256), 0, st, mask, n, nw, order, keep, count);
+  const BatchWs w = batch_ws(work, n, n * ((n + 63) / 64), false);
+  hipLaunchKernelGGL(nms_rank_kernel, dim3(ivit_cdiv(n, 256)), dim3(256), 0, st, scores, n, w.order);
+  hipLaunchKernelGGL(nms_sorted_boxes_kernel, dim3(ivit_cdiv(n, 256)), dim3(256), 0, st, boxes_xywha, w.order, n, w.sb);
+  nms_mask_and_scan(boxes_xywha, w.order, w.sb, nullptr, nullptr, w.mask, SegView{nullptr, nullptr, nullptr, n, 0}, 1,
+                    n, iou_thr, false, keep, count, st);
   IVIT_LAUNCH_CHECK();
   return 0;
 }
 
-// Batched torchvision-CPU-exact NMS (eval_vit.py:170 per sample, all samples in one launch per
-// stage). seg: [S+1] int64 row offsets (device); mask_off: [S] int64 word offsets of each
-// sample's [n_s, ceil(n_s/64)] suppression mask (device). keep[seg[s] ..] receives sample s's kept
-// LOCAL indices in score order, count[s] their number. The score order is a stable descending
-// sort (nms_sort_b_kernel: one workgroup per sample; ties keep the row order, as torch's stable
-// sort). Workspace: ivit_nms_batched_workspace(n_samples, total, mask_words) bytes.
-namespace {
-long al16(long b) { return (b + 15) / 16 * 16; }
-}  // namespace
-
+// seg: [S+1] int64 row offsets (device); mask_off: [S] int64 word offsets of each sample's
+// [n_s, ceil(n_s/64)] suppression mask (device).
 extern "C" long ivit_nms_batched_workspace(long n_samples, long total, long mask_words) {
-  if (n_samples <= 0 || total <= 0) return 64;
-  return al16(4 * total) + al16(20 * total) + al16(8 * mask_words) + 4 * al16(4 * total) + 64;
+  return batch_ws_bytes(n_samples, total, mask_words, false);
 }
 
 extern "C" int ivit_nms_batched(const float* boxes_xywha, const float* scores, const long* seg, const long* mask_off,
                                 long n_samples, long total, long max_n, long mask_words, double iou_thr, long* keep,
                                 long* count, void* work, long work_bytes, void* stream) {
-  IVIT_CHECK_ARG(max_n <= 64L * NMS_MAXW, "ivit_nms_batched: n=%ld exceeds %d", max_n, 64 * NMS_MAXW);
-  IVIT_CHECK_ARG(n_samples < 65536 && total < (1L << 31), "ivit_nms_batched: too many samples / rows (%ld, %ld)",
-                 n_samples, total);
-  IVIT_CHECK_ARG(work_bytes >= ivit_nms_batched_workspace(n_samples, total, mask_words),
-                 "ivit_nms_batched: workspace too small");
-  hipStream_t st = ivit_stream(stream);
-  if (n_samples <= 0) return 0;
-  if (max_n <= 0) {
-    (void)hipMemsetAsync(count, 0, sizeof(long) * n_samples, st);
-    IVIT_LAUNCH_CHECK();
-    return 0;
-  }
-  const int nwmax = (int)((max_n + 63) / 64);
-  char* w = (char*)(((uintptr_t)work + 15) & ~(uintptr_t)15);
-  int* order = (int*)w;
-  w += al16(4 * total);
-  float* sb = (float*)w;
-  w += al16(20 * total);
-  unsigned long long* mask = (unsigned long long*)w;
-  w += al16(8 * mask_words);
-  unsigned* k0 = (unsigned*)w;
-  w += al16(4 * total);
-  unsigned* k1 = (unsigned*)w;
-  w += al16(4 * total);
-  int* v0 = (int*)w;
-  w += al16(4 * total);
-  int* v1 = (int*)w;
-  const SegView sv{seg, mask_off, nullptr, 0, 0};
-  hipLaunchKernelGGL(nms_sort_b_kernel, dim3(n_samples), dim3(PS_T), 0, st, boxes_xywha, scores, seg, k0, v0, k1, v1,
-                     order, sb);
-  hipLaunchKernelGGL(nms_mask_b_kernel, dim3(ivit_cdiv(nwmax, NMS_CB), nwmax, n_samples), dim3(64), 0, st, sb, sv,
-                     nms_thr(iou_thr), mask);
-  hipLaunchKernelGGL(nms_scan_b_kernel, dim3(n_samples), dim3(256), 0, st, mask, sv, order, keep, count);
-  IVIT_LAUNCH_CHECK();
-  return 0;
+  return nms_batched_impl("ivit_nms_batched", false, boxes_xywha, scores, seg, mask_off, n_samples, total, max_n,
+                          mask_words, iou_thr, keep, count, work, work_bytes, stream);
 }
 
-// Rotated form of ivit_nms_batched: the axis workspace (the sort stage is shared and still writes
-// its corner rows) plus the per-box polygons (80 B per row) and prefilter records (32 B per row).
 extern "C" long ivit_nms_rotated_batched_workspace(long n_samples, long total, long mask_words) {
-  if (n_samples <= 0 || total <= 0) return 64;
-  return ivit_nms_batched_workspace(n_samples, total, mask_words) + al16(80 * total) + al16(32 * total);
+  return batch_ws_bytes(n_samples, total, mask_words, true);
 }
 
 extern "C" int ivit_nms_rotated_batched(const float* boxes_xywha, const float* scores, const long* seg,
                                         const long* mask_off, long n_samples, long total, long max_n, long mask_words,
                                         double iou_thr, long* keep, long* count, void* work, long work_bytes,
                                         void* stream) {
-  IVIT_CHECK_ARG(max_n <= 64L * NMS_MAXW, "ivit_nms_rotated_batched: n=%ld exceeds %d", max_n, 64 * NMS_MAXW);
-  IVIT_CHECK_ARG(n_samples < 65536 && total < (1L << 31),
-                 "ivit_nms_rotated_batched: too many samples / rows (%ld, %ld)", n_samples, total);
-  IVIT_CHECK_ARG(work_bytes >= ivit_nms_rotated_batched_workspace(n_samples, total, mask_words),
-                 "ivit_nms_rotated_batched: workspace too small");
-  hipStream_t st = ivit_stream(stream);
-  if (n_samples <= 0) return 0;
-  if (max_n <= 0 || total <= 0) {
-    (void)hipMemsetAsync(count, 0, sizeof(long) * n_samples, st);
-    IVIT_LAUNCH_CHECK();
-    return 0;
-  }
-  const int nwmax = (int)((max_n + 63) / 64);
-  char* w = (char*)(((uintptr_t)work + 15) & ~(uintptr_t)15);
-  int* order = (int*)w;
-  w += al16(4 * total);
-  float* sb = (float*)w;
-  w += al16(20 * total);
-  unsigned long long* mask = (unsigned long long*)w;
-  w += al16(8 * mask_words);
-  unsigned* k0 = (unsigned*)w;
-  w += al16(4 * total);
-  unsigned* k1 = (unsigned*)w;
-  w += al16(4 * total);
-  int* v0 = (int*)w;
-  w += al16(4 * total);
-  int* v1 = (int*)w;
-  w += al16(4 * total);
-  double* rp = (double*)w;
-  w += al16(80 * total);
-  float4* rc = (float4*)w;
-  const SegView sv{seg, mask_off, nullptr, 0, 0};
-  hipLaunchKernelGGL(nms_sort_b_kernel, dim3(n_samples), dim3(PS_T), 0, st, boxes_xywha, scores, seg, k0, v0, k1, v1,
-                     order, sb);
-  hipLaunchKernelGGL(nms_rot_prep_kernel, dim3(ivit_cdiv(max_n, 256), n_samples), dim3(256), 0, st, boxes_xywha, order,
-                     sv, rp, rc);
-  hipLaunchKernelGGL(nms_rot_mask_b_kernel, dim3(ivit_cdiv(nwmax, NMS_CB), nwmax, n_samples), dim3(64), 0, st, rp, rc,
-                     sv, iou_thr, iou_thr >= 0.0 ? 1 : 0, mask);
-  hipLaunchKernelGGL(nms_rot_scan_b_kernel, dim3(n_samples), dim3(256), 0, st, mask, sv, order, keep, count);
-  IVIT_LAUNCH_CHECK();
-  return 0;
+  return nms_batched_impl("ivit_nms_rotated_batched", true, boxes_xywha, scores, seg, mask_off, n_samples, total,
+                          max_n, mask_words, iou_thr, keep, count, work, work_bytes, stream);
 }
 
-// Eval post-processing for a batch (eval_vit.py:156-176): four launches, no host round trip.
+// Eval post-processing for a batch (eval_vit.py:156-176): four launches (five with the rotated
+// test: the per-box polygons are one more), no host round trip.
 namespace {
+// The workspace: one region per PostWs member in the member order, then (rotated only) rp and rc,
+// each rounded up to 16 bytes, plus 16 of slack for rounding the base up. The mask is reserved
+// for the worst case, every anchor of every sample passing.
+constexpr int POST_REGIONS = 14;
 struct PostLayout {
   long bytes;
-  long off[12];
+  long off[POST_REGIONS];
+  int regions;  // 12, or 14 with rotated
 };
-PostLayout post_layout(long B, long NA) {
+PostLayout post_layout(long B, long NA, bool rotated) {
   const long R = B * NA, nw = (NA + 63) / 64;
-  const long sz[12] = {4 * B, 4 * R, 4 * R, 20 * R, 4 * R, 4 * R, 4 * R, 4 * R, 4 * R, 20 * R, 8 * R, 8 * R * nw};
-  PostLayout L{0, {}};
-  for (int i = 0; i < 12; ++i) {
+  const long sz[POST_REGIONS] = {4 * B, 4 * R, 4 * R, 20 * R, 4 * R,      4 * R,  4 * R,
+                                 4 * R, 4 * R, 20 * R, 8 * R, 8 * R * nw, 80 * R, 32 * R};
+  PostLayout L{0, {}, rotated ? 14 : 12};
+  for (int i = 0; i < L.regions; ++i) {
     L.off[i] = L.bytes;
     L.bytes += al16(sz[i]);
   }
   L.bytes += 16;  // alignment slack
   return L;
 }
-}  // namespace
-
-extern "C" long ivit_eval_post_workspace(long B, long NA) {
+long post_ws_bytes(long B, long NA, bool rotated) {
   if (B <= 0 || NA <= 0) return 64;
-  return post_layout(B, NA).bytes;
+  return post_layout(B, NA, rotated).bytes;
+}
+PostWs post_ws(void* work, long B, long NA, bool rotated) {
+  const PostLayout L = post_layout(B, NA, rotated);
+  char* base = (char*)(((uintptr_t)work + 15) & ~(uintptr_t)15);
+  auto at = [&](int i) -> void* { return i < L.regions ? base + L.off[i] : nullptr; };
+  PostWs w;
+  w.n = (int*)at(0);
+  w.anchor = (int*)at(1);
+  w.score = (float*)at(2);
+  w.box = (float*)at(3);
+  w.k0 = (unsigned*)at(4);
+  w.k1 = (unsigned*)at(5);
+  w.v0 = (int*)at(6);
+  w.v1 = (int*)at(7);
+  w.order = (int*)at(8);
+  w.sb = (float*)at(9);
+  w.keep = (long*)at(10);
+  w.mask = (unsigned long long*)at(11);
+  w.rp = (double*)at(12);
+  w.rc = (float4*)at(13);
+  return w;
 }
 
-extern "C" int ivit_eval_post(const float* cls, const float* box_rel, const float* intent, const float* anchors, long B,
-                              long NA, long K, float conf_thr, double iou_thr, float* out_scores, float* out_boxes,
-                              long* out_intent, long* out_count, void* work, long work_bytes, void* stream) {
-  IVIT_CHECK_ARG(B >= 0 && B < 65536 && NA >= 0 && K >= 1, "ivit_eval_post: bad sizes (B %ld, NA %ld, K %ld)", B, NA,
-                 K);
-  IVIT_CHECK_ARG(NA <= 64L * NMS_MAXW, "ivit_eval_post: NA=%ld exceeds %d", NA, 64 * NMS_MAXW);
-  IVIT_CHECK_ARG(work_bytes >= ivit_eval_post_workspace(B, NA), "ivit_eval_post: workspace too small");
+int eval_post_impl(const char* name, bool rotated, const float* cls, const float* box_rel, const float* intent,
+                   const float* anchors, long B, long NA, long K, float conf_thr, double iou_thr, float* out_scores,
+                   float* out_boxes, long* out_intent, long* out_count, void* work, long work_bytes, void* stream) {
+  IVIT_CHECK_ARG(B >= 0 && B < 65536 && NA >= 0 && K >= 1, "%s: bad sizes (B %ld, NA %ld, K %ld)", name, B, NA, K);
+  IVIT_CHECK_ARG(NA <= 64L * NMS_MAXW, "%s: NA=%ld exceeds %d", name, NA, 64 * NMS_MAXW);
+  IVIT_CHECK_ARG(work_bytes >= post_ws_bytes(B, NA, rotated), "%s: workspace too small", name);
   hipStream_t st = ivit_stream(stream);
   if (B == 0) return 0;
   if (NA == 0) {
     (void)hipMemsetAsync(out_count, 0, sizeof(long) * B, st);
-    IVIT_LAUNCH_CHECK();
-    return 0;
+    return launch_status(name);
   }
-  const PostLayout L = post_layout(B, NA);
-  char* base = (char*)(((uintptr_t)work + 15) & ~(uintptr_t)15);
-  PostWs w;
-  w.n = (int*)(base + L.off[0]);
-  w.anchor = (int*)(base + L.off[1]);
-  w.score = (float*)(base + L.off[2]);
-  w.box = (float*)(base + L.off[3]);
-  w.k0 = (unsigned*)(base + L.off[4]);
-  w.k1 = (unsigned*)(base + L.off[5]);
-  w.v0 = (int*)(base + L.off[6]);
-  w.v1 = (int*)(base + L.off[7]);
-  w.order = (int*)(base + L.off[8]);
-  w.sb = (float*)(base + L.off[9]);
-  w.keep = (long*)(base + L.off[10]);
-  w.mask = (unsigned long long*)(base + L.off[11]);
-  const int nw = (int)((NA + 63) / 64);
-  const SegView sv{nullptr, nullptr, w.n, NA, NA * nw};
+  const PostWs w = post_ws(work, B, NA, rotated);
+  const SegView sv{nullptr, nullptr, w.n, NA, NA * ((NA + 63) / 64)};
   hipLaunchKernelGGL(post_select_kernel, dim3(B), dim3(PS_T), 0, st, cls, box_rel, anchors, (int)NA, conf_thr, w);
-  hipLaunchKernelGGL(nms_mask_b_kernel, dim3(ivit_cdiv(nw, NMS_CB), nw, B), dim3(64), 0, st, w.sb, sv,
-                     nms_thr(iou_thr), w.mask);
-  hipLaunchKernelGGL(nms_scan_b_kernel, dim3(B), dim3(256), 0, st, w.mask, sv, w.order, w.keep, out_count);
+  nms_mask_and_scan(w.box, w.order, w.sb, w.rp, w.rc, w.mask, sv, B, NA, iou_thr, rotated, w.keep, out_count, st);
   hipLaunchKernelGGL(post_gather_kernel, dim3(ivit_cdiv(NA, 256), B), dim3(256), 0, st, out_count, intent, (int)NA,
                      (int)K, w, out_scores, out_boxes, out_intent);
-  IVIT_LAUNCH_CHECK();
-  return 0;
+  return launch_status(name);
+}
+}  // namespace
+
+extern "C" long ivit_eval_post_workspace(long B, long NA) { return post_ws_bytes(B, NA, false); }
+
+extern "C" int ivit_eval_post(const float* cls, const float* box_rel, const float* intent, const float* anchors, long B,
+                              long NA, long K, float conf_thr, double iou_thr, float* out_scores, float* out_boxes,
+                              long* out_intent, long* out_count, void* work, long work_bytes, void* stream) {
+  return eval_post_impl("ivit_eval_post", false, cls, box_rel, intent, anchors, B, NA, K, conf_thr, iou_thr,
+                        out_scores, out_boxes, out_intent, out_count, work, work_bytes, stream);
 }
 
-// ivit_eval_post with the rotated suppression test: five launches (the per-box polygons are one
-// more), the same outputs. The workspace is the axis one plus 112 B per row.
-extern "C" long ivit_eval_post_rotated_workspace(long B, long NA) {
-  if (B <= 0 || NA <= 0) return 64;
-  return post_layout(B, NA).bytes + al16(80 * B * NA) + al16(32 * B * NA);
-}
+extern "C" long ivit_eval_post_rotated_workspace(long B, long NA) { return post_ws_bytes(B, NA, true); }
 
 extern "C" int ivit_eval_post_rotated(const float* cls, const float* box_rel, const float* intent, const float* anchors,
                                       long B, long NA, long K, float conf_thr, double iou_thr, float* out_scores,
                                       float* out_boxes, long* out_intent, long* out_count, void* work, long work_bytes,
                                       void* stream) {
-  IVIT_CHECK_ARG(B >= 0 && B < 65536 && NA >= 0 && K >= 1, "ivit_eval_post_rotated: bad sizes (B %ld, NA %ld, K %ld)",
-                 B, NA, K);
-  IVIT_CHECK_ARG(NA <= 64L * NMS_MAXW, "ivit_eval_post_rotated: NA=%ld exceeds %d", NA, 64 * NMS_MAXW);
-  IVIT_CHECK_ARG(work_bytes >= ivit_eval_post_rotated_workspace(B, NA), "ivit_eval_post_rotated: workspace too small");
-  hipStream_t st = ivit_stream(stream);
-  if (B == 0) return 0;
-  if (NA == 0) {
-    (void)hipMemsetAsync(out_count, 0, sizeof(long) * B, st);
-    IVIT_LAUNCH_CHECK();
-    return 0;
-  }
-  const PostLayout L = post_layout(B, NA);
-  char* base = (char*)(((uintptr_t)work + 15) & ~(uintptr_t)15);
-  PostWs w;
-  w.n = (int*)(base + L.off[0]);
-  w.anchor = (int*)(base + L.off[1]);
-  w.score = (float*)(base + L.off[2]);
-  w.box = (float*)(base + L.off[3]);
-  w.k0 = (unsigned*)(base + L.off[4]);
-  w.k1 = (unsigned*)(base + L.off[5]);
-  w.v0 = (int*)(base + L.off[6]);
-  w.v1 = (int*)(base + L.off[7]);
-  w.order = (int*)(base + L.off[8]);
-  w.sb = (float*)(base + L.off[9]);
-  w.keep = (long*)(base + L.off[10]);
-  w.mask = (unsigned long long*)(base + L.off[11]);
-  const long tail = L.off[11] + al16(8 * B * NA * ((NA + 63) / 64));
-  double* rp = (double*)(base + tail);
-  float4* rc = (float4*)(base + tail + al16(80 * B * NA));
-  const int nw = (int)((NA + 63) / 64);
-  const SegView sv{nullptr, nullptr, w.n, NA, NA * nw};
-  hipLaunchKernelGGL(post_select_kernel, dim3(B), dim3(PS_T), 0, st, cls, box_rel, anchors, (int)NA, conf_thr, w);
-  hipLaunchKernelGGL(nms_rot_prep_kernel, dim3(ivit_cdiv(NA, 256), B), dim3(256), 0, st, w.box, w.order, sv, rp, rc);
-  hipLaunchKernelGGL(nms_rot_mask_b_kernel, dim3(ivit_cdiv(nw, NMS_CB), nw, B), dim3(64), 0, st, rp, rc, sv, iou_thr,
-                     iou_thr >= 0.0 ? 1 : 0, w.mask);
-  hipLaunchKernelGGL(nms_rot_scan_b_kernel, dim3(B), dim3(256), 0, st, w.mask, sv, w.order, w.keep, out_count);
-  hipLaunchKernelGGL(post_gather_kernel, dim3(ivit_cdiv(NA, 256), B), dim3(256), 0, st, out_count, intent, (int)NA,
-                     (int)K, w, out_scores, out_boxes, out_intent);
-  IVIT_LAUNCH_CHECK();
-  return 0;
+  return eval_post_impl("ivit_eval_post_rotated", true, cls, box_rel, intent, anchors, B, NA, K, conf_thr, iou_thr,
+                        out_scores, out_boxes, out_intent, out_count, work, work_bytes, stream);
 }
+

@@ -222,7 +222,10 @@ class PostPipeline:
         if self.stream is None:
             return _post_collect(p)
         with torch.cuda.stream(self.stream):  # the count read waits for this batch's kernels only
-            return _post_collect(p)
+            out = _post_collect(p)
+        # the outputs were allocated and written on self.stream and are consumed on the caller's
+        torch.cuda.current_stream(p[0].device).wait_stream(self.stream)
+        return out
 
     def push(self, cls_logits, box_preds_rel, intent_logits):
         prev = self._collect()  # batch k-1: its post-processing ran beside this batch's forward
