@@ -340,6 +340,37 @@ int ivit_adamw_chunked(long n_tensors, void* const* params, void* const* grads, 
                        void* const* exp_avg_sq, void* const* shadows, const long* sizes, const int* chunks,
                        long n_chunks, float lr, double beta1, double beta2, float eps, float weight_decay, float bc1,
                        float bc2_sqrt, const float* finite, const float* steps_in, float* steps_out, void* stream);
+/* ivit_adamw_chunked with a device gradient scale: every gradient element is multiplied by
+ * *grad_scale (device f32; null = no multiply, bit-identical to ivit_adamw_chunked) in f32 as it is
+ * loaded, before the update; the gradient arrays themselves are not written. With the coef of
+ * ivit_grad_norm it is the update torch.nn.utils.clip_grad_norm_ + AdamW make, without the scale pass. */
+int ivit_adamw_chunked_scaled(long n_tensors, void* const* params, void* const* grads, void* const* exp_avg,
+                              void* const* exp_avg_sq, void* const* shadows, const long* sizes, const int* chunks,
+                              long n_chunks, float lr, double beta1, double beta2, float eps, float weight_decay,
+                              float bc1, float bc2_sqrt, const float* finite, const float* steps_in,
+                              float* steps_out, const float* grad_scale, void* stream);
+
+/* ---- Global gradient norm / clipping (torch.nn.utils.clip_grad_norm_, norm_type 2). ---------- */
+/* L2 norm over n_tensors f32 tensors given as ivit_adamw_chunked takes them (pointer table, sizes,
+ * (tensor, chunk) table). Two launches, no atomics, bitwise repeatable and independent of the
+ * tensors' alignment: one workgroup per chunk sums the squares in f64 into workspace
+ * (ivit_grad_norm_workspace(n_chunks) bytes, 8-B aligned), one workgroup adds the partials in a
+ * fixed order and writes result (device f32 [4]):
+ *   result[0] norm   = (float)sqrt(sum)
+ *   result[1] coef   = min(1, max_norm / (norm + 1e-6f))   (1 when the norm is not finite)
+ *   result[2] finite = (finite_in == null || *finite_in != 0) && isfinite(norm), as 1.0 / 0.0
+ *   result[3] 0
+ * stats (optional, device f64 [5], zeroed by the caller) accumulates over calls: calls, calls with
+ * coef < 1, calls with a non-finite norm, sum and max of the finite norms. n_chunks == 0 writes
+ * norm 0, coef 1. max_norm must be > 0. */
+long ivit_grad_norm_workspace(long n_chunks);
+int ivit_grad_norm(long n_tensors, void* const* grads, const long* sizes, const int* chunks, long n_chunks,
+                   float max_norm, const float* finite_in, void* workspace, long workspace_bytes, float* result,
+                   double* stats, void* stream);
+/* g *= *coef (device f32) in place over the same tensor list and chunk grid; nothing is written
+ * when *coef == 1. */
+int ivit_grad_scale(long n_tensors, void* const* grads, const long* sizes, const int* chunks, long n_chunks,
+                    const float* coef, void* stream);
 
 /* ---- Detection / intention loss (loss.py:58-206): assignment + focal + Smooth-L1 + CE. ----- */
 /* gt: [B, Gmax, 5] f32 padded, ngt[B] int32, gint[B, Gmax] int32. keep: [B, NA] f32 0/1 (dominant

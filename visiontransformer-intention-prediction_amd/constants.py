@@ -60,3 +60,6 @@ DETECTION_IOU_THRESHOLDS = [0.5, 0.6, 0.7, 0.8, 0.9]
 IOU_THRESHOLD_FOR_INTENTION_MATCH = 0.5
 EVAL_USE_ROTATED_IOU = False
 EVAL_USE_ROTATED_NMS = False  # eval_vit.py --rotated-nms: suppress on the rotated IoU of the decoded boxes
+
+# train_vit.py / train_cnn.py --clip-grad-norm: global gradient L2-norm bound (None: no clipping, the reference's loop)
+GRAD_CLIP_NORM = None

@@ -180,13 +180,22 @@ __global__ __launch_bounds__(256) void adamw_kernel(void* const* params, void* c
 // tensor (335 k for IntentNetViT's 327 parameters, nearly all of them leaving at once), which kept
 // the update at ~3.7 TB/s; this grid has exactly the ~15.7 k chunks there are. Same element update
 // (adamw_elem): bit-identical results.
+// SCALED (ivit_adamw_chunked_scaled): every gradient element is first multiplied by *grad_scale (the
+// clip coefficient of ivit_grad_norm) — the product ivit_grad_scale would have stored, so the fused and
+// the unfused form give the same bits. The unscaled instantiation is the kernel as it was.
 constexpr int AW_CHUNK = 4096;
+IVIT_DEV float scaled_grad(float g, float s) {
+#pragma clang fp contract(off)
+  return g * s;
+}
+template <bool SCALED>
 __global__ __launch_bounds__(256) void adamw_chunk_kernel(void* const* params, void* const* grads, void* const* ms,
                                                           void* const* vs, const long* sizes, const int2* chunks,
                                                           float lr, float b2, float eps, float wd, float bc1,
                                                           float bc2s, void* const* shadows, const float* finite,
                                                           const float* steps_in, float* steps_out, double b1d,
-                                                          double b2d, float omb1, float omb2) {
+                                                          double b2d, float omb1, float omb2,
+                                                          const float* grad_scale) {
   const int2 ck = chunks[blockIdx.x];
   const int t = ck.x;
   const bool go = finite == nullptr || *finite != 0.f;
@@ -208,7 +217,10 @@ __global__ __launch_bounds__(256) void adamw_chunk_kernel(void* const* params, v
   float* v = (float*)vs[t] + off;
   bf16* sh = shadows && shadows[t] ? (bf16*)shadows[t] + off : nullptr;
   const float step = lr / bc1, keep = 1.f - lr * wd;
+  float gs = 1.f;
+  if constexpr (SCALED) gs = *grad_scale;
   auto upd = [&](float gi, float& pi, float& mi, float& vi) {
+    if constexpr (SCALED) gi = scaled_grad(gi, gs);
     adamw_elem(gi, pi, mi, vi, keep, omb1, b2, omb2, bc2s, eps, step);
   };
   const bool vec = ((((uintptr_t)p | (uintptr_t)g | (uintptr_t)m | (uintptr_t)v) & 15) == 0) &&
@@ -235,6 +247,129 @@ __global__ __launch_bounds__(256) void adamw_chunk_kernel(void* const* params, v
       v[i] = vi;
       if (sh) sh[i] = (bf16)pi;
     }
+  }
+}
+
+// ---- global gradient norm (ivit_grad_norm) ----
+// Sum of a per-thread f64 value over the NW waves of the workgroup, in one fixed order: xor
+// butterfly inside each wave (every lane ends with the same bits: IEEE addition commutes), then
+// waves 0 .. NW-1 in order. Valid in thread 0.
+template <int NW>
+IVIT_DEV double block_sum_f64(double v, double* red) {
+#pragma unroll
+  for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o, 64);
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
+  __syncthreads();
+  double t = red[0];
+#pragma unroll
+  for (int w = 1; w < NW; ++w) t += red[w];
+  return t;
+}
+
+// Pass 1: one workgroup per chunk. Thread t owns elements 4t .. 4t+3 (+1024k) of the chunk and adds
+// their squares to its f64 sum in index order; the ownership and the order of every add are the
+// same whether the four floats come from one 16-B load or from four 4-B loads (a chunk that is not
+// 16-B aligned, or its ragged end), so the partial does not depend on where the tensor lies. The
+// square of an f32 is exact in f64 (48 significant bits) and neither overflows nor underflows.
+__global__ __launch_bounds__(256) void grad_sumsq_kernel(void* const* grads, const long* sizes, const int2* chunks,
+                                                         double* part) {
+  __shared__ double red[4];
+  const int2 ck = chunks[blockIdx.x];
+  const long off = (long)ck.y * AW_CHUNK;
+  const int len = (int)min((long)AW_CHUNK, sizes[ck.x] - off);
+  const float* g = (const float*)grads[ck.x] + off;
+  const bool al = al16(g);
+  float4 x[AW_CHUNK / 1024];
+#pragma unroll
+  for (int k = 0; k < AW_CHUNK / 1024; ++k) {
+    const int i = threadIdx.x * 4 + k * 1024;
+    if (al && i + 4 <= len) {
+      x[k] = *(const float4*)(g + i);
+    } else {
+      x[k].x = i < len ? g[i] : 0.f;
+      x[k].y = i + 1 < len ? g[i + 1] : 0.f;
+      x[k].z = i + 2 < len ? g[i + 2] : 0.f;
+      x[k].w = i + 3 < len ? g[i + 3] : 0.f;
+    }
+  }
+  double s = 0.0;
+#pragma unroll
+  for (int k = 0; k < AW_CHUNK / 1024; ++k) {
+    const double a = x[k].x, b = x[k].y, c = x[k].z, d = x[k].w;
+    s += a * a;  // exact products: fused or not, the same bits
+    s += b * b;
+    s += c * c;
+    s += d * d;
+  }
+  s = block_sum_f64<4>(s, red);
+  if (threadIdx.x == 0) part[blockIdx.x] = s;
+}
+
+// Pass 2: one workgroup of GN_FINAL threads. Thread t adds partials t, t + GN_FINAL, ... in order
+// (loaded eight at a time: a load per add would serialise ~15 L2 round trips), then the same
+// workgroup sum; thread 0 writes the record {norm, coef, finite, 0} (clip_grad_norm_'s formula and
+// clamp in f32) and updates the optional f64 stats {calls, clipped, non-finite, sum, max of finite
+// norms}.
+constexpr int GN_FINAL = 1024;
+__global__ __launch_bounds__(GN_FINAL) void grad_norm_final_kernel(const double* part, int n, float max_norm,
+                                                                   const float* finite_in, float* result,
+                                                                   double* stats) {
+#pragma clang fp contract(off)
+  __shared__ double red[GN_FINAL / 64];
+  double s = 0.0;
+  for (int i0 = threadIdx.x; i0 < n; i0 += 8 * GN_FINAL) {
+    double v[8];
+#pragma unroll
+    for (int k = 0; k < 8; ++k) {
+      const int i = i0 + k * GN_FINAL;
+      v[k] = i < n ? part[i] : 0.0;
+    }
+#pragma unroll
+    for (int k = 0; k < 8; ++k) s += v[k];  // + 0.0 past the end: the bits of a sum of squares stay
+  }
+  s = block_sum_f64<GN_FINAL / 64>(s, red);
+  if (threadIdx.x != 0) return;
+  const float norm = (float)sqrt(s);
+  const bool nf = isfinite(norm);
+  const float q = max_norm / (norm + 1e-6f);
+  const float coef = nf ? (q < 1.f ? q : 1.f) : 1.f;
+  result[0] = norm;
+  result[1] = coef;
+  result[2] = ((finite_in == nullptr || *finite_in != 0.f) && nf) ? 1.f : 0.f;
+  result[3] = 0.f;
+  if (stats != nullptr) {
+    stats[0] += 1.0;
+    if (coef < 1.f) stats[1] += 1.0;
+    if (!nf) stats[2] += 1.0;
+    if (nf) {
+      stats[3] += (double)norm;
+      if ((double)norm > stats[4]) stats[4] = (double)norm;
+    }
+  }
+}
+
+// g *= *coef over the chunk grid (the second half of clip_grad_norm_). The products are the ones
+// adamw_chunk_kernel<true> forms in registers. coef == 1 (no clipping) would rewrite every element
+// with itself: nothing is stored.
+__global__ __launch_bounds__(256) void grad_scale_kernel(void* const* grads, const long* sizes, const int2* chunks,
+                                                         const float* coef) {
+  const float c = *coef;
+  if (c == 1.f) return;
+  const int2 ck = chunks[blockIdx.x];
+  const long off = (long)ck.y * AW_CHUNK;
+  const int len = (int)min((long)AW_CHUNK, sizes[ck.x] - off);
+  float* g = (float*)grads[ck.x] + off;
+  if (al16(g) && (len & 3) == 0) {
+    for (int i = threadIdx.x * 4; i < len; i += 1024) {
+      float4 v = *(const float4*)(g + i);
+      v.x = scaled_grad(v.x, c);
+      v.y = scaled_grad(v.y, c);
+      v.z = scaled_grad(v.z, c);
+      v.w = scaled_grad(v.w, c);
+      *(float4*)(g + i) = v;
+    }
+  } else {
+    for (int i = threadIdx.x; i < len; i += 256) g[i] = scaled_grad(g[i], c);
   }
 }
 
@@ -351,10 +486,73 @@ extern "C" int ivit_adamw_chunked(long n_tensors, void* const* params, void* con
   IVIT_CHECK_ARG((steps_in == nullptr) == (steps_out == nullptr), "ivit_adamw_chunked: steps_in / steps_out pair");
   IVIT_CHECK_ARG(steps_in == nullptr || steps_in != steps_out, "ivit_adamw_chunked: steps_out aliases steps_in");
   IVIT_CHECK_ARG(((uintptr_t)chunks & 7) == 0, "ivit_adamw_chunked: misaligned chunk table");
-  hipLaunchKernelGGL(adamw_chunk_kernel, dim3((unsigned)n_chunks), dim3(256), 0, ivit_stream(stream), params, grads,
-                     exp_avg, exp_avg_sq, sizes, (const int2*)chunks, lr, (float)beta2, eps, weight_decay, bc1,
+  hipLaunchKernelGGL(adamw_chunk_kernel<false>, dim3((unsigned)n_chunks), dim3(256), 0, ivit_stream(stream), params,
+                     grads, exp_avg, exp_avg_sq, sizes, (const int2*)chunks, lr, (float)beta2, eps, weight_decay, bc1,
                      bc2_sqrt, shadows, finite, steps_in, steps_out, beta1, beta2, (float)(1.0 - beta1),
-                     (float)(1.0 - beta2));
+                     (float)(1.0 - beta2), (const float*)nullptr);
+  IVIT_LAUNCH_CHECK();
+  return 0;
+}
+
+extern "C" int ivit_adamw_chunked_scaled(long n_tensors, void* const* params, void* const* grads,
+                                         void* const* exp_avg, void* const* exp_avg_sq, void* const* shadows,
+                                         const long* sizes, const int* chunks, long n_chunks, float lr, double beta1,
+                                         double beta2, float eps, float weight_decay, float bc1, float bc2_sqrt,
+                                         const float* finite, const float* steps_in, float* steps_out,
+                                         const float* grad_scale, void* stream) {
+  if (grad_scale == nullptr)
+    return ivit_adamw_chunked(n_tensors, params, grads, exp_avg, exp_avg_sq, shadows, sizes, chunks, n_chunks, lr,
+                              beta1, beta2, eps, weight_decay, bc1, bc2_sqrt, finite, steps_in, steps_out, stream);
+  if (n_tensors <= 0 || n_chunks <= 0) return 0;
+  IVIT_CHECK_ARG(chunks != nullptr && n_chunks < (1L << 31), "ivit_adamw_chunked_scaled: bad chunk table");
+  IVIT_CHECK_ARG((steps_in == nullptr) == (steps_out == nullptr),
+                 "ivit_adamw_chunked_scaled: steps_in / steps_out pair");
+  IVIT_CHECK_ARG(steps_in == nullptr || steps_in != steps_out, "ivit_adamw_chunked_scaled: steps_out aliases steps_in");
+  IVIT_CHECK_ARG(((uintptr_t)chunks & 7) == 0, "ivit_adamw_chunked_scaled: misaligned chunk table");
+  hipLaunchKernelGGL(adamw_chunk_kernel<true>, dim3((unsigned)n_chunks), dim3(256), 0, ivit_stream(stream), params,
+                     grads, exp_avg, exp_avg_sq, sizes, (const int2*)chunks, lr, (float)beta2, eps, weight_decay, bc1,
+                     bc2_sqrt, shadows, finite, steps_in, steps_out, beta1, beta2, (float)(1.0 - beta1),
+                     (float)(1.0 - beta2), grad_scale);
+  IVIT_LAUNCH_CHECK();
+  return 0;
+}
+
+extern "C" long ivit_grad_norm_workspace(long n_chunks) { return (n_chunks > 0 ? n_chunks : 1) * (long)sizeof(double); }
+
+extern "C" int ivit_grad_norm(long n_tensors, void* const* grads, const long* sizes, const int* chunks, long n_chunks,
+                              float max_norm, const float* finite_in, void* workspace, long workspace_bytes,
+                              float* result, double* stats, void* stream) {
+  IVIT_CHECK_ARG(max_norm > 0.f, "ivit_grad_norm: max_norm must be > 0 (got %g)", (double)max_norm);  // NaN fails too
+  IVIT_CHECK_ARG(n_tensors >= 0 && n_chunks >= 0 && n_chunks < (1L << 31), "ivit_grad_norm: bad counts");
+  IVIT_CHECK_ARG(n_tensors == 0 || (grads != nullptr && sizes != nullptr), "ivit_grad_norm: null tensor tables");
+  IVIT_CHECK_ARG(n_chunks == 0 || (n_tensors > 0 && chunks != nullptr), "ivit_grad_norm: null chunk table");
+  IVIT_CHECK_ARG(((uintptr_t)chunks & 7) == 0, "ivit_grad_norm: misaligned chunk table");
+  IVIT_CHECK_ARG(result != nullptr, "ivit_grad_norm: result is null");
+  IVIT_CHECK_ARG(workspace != nullptr && ((uintptr_t)workspace & 7) == 0 &&
+                     workspace_bytes >= ivit_grad_norm_workspace(n_chunks),
+                 "ivit_grad_norm: workspace too small or misaligned (%ld bytes, need %ld)", workspace_bytes,
+                 ivit_grad_norm_workspace(n_chunks));
+  IVIT_CHECK_ARG(((uintptr_t)stats & 7) == 0, "ivit_grad_norm: misaligned stats");
+  if (n_chunks > 0) {
+    hipLaunchKernelGGL(grad_sumsq_kernel, dim3((unsigned)n_chunks), dim3(256), 0, ivit_stream(stream), grads, sizes,
+                       (const int2*)chunks, (double*)workspace);
+    IVIT_LAUNCH_CHECK();
+  }
+  hipLaunchKernelGGL(grad_norm_final_kernel, dim3(1), dim3(GN_FINAL), 0, ivit_stream(stream), (const double*)workspace,
+                     (int)n_chunks, max_norm, finite_in, result, stats);
+  IVIT_LAUNCH_CHECK();
+  return 0;
+}
+
+extern "C" int ivit_grad_scale(long n_tensors, void* const* grads, const long* sizes, const int* chunks, long n_chunks,
+                               const float* coef, void* stream) {
+  if (n_tensors <= 0 || n_chunks <= 0) return 0;
+  IVIT_CHECK_ARG(grads != nullptr && sizes != nullptr, "ivit_grad_scale: null tensor tables");
+  IVIT_CHECK_ARG(chunks != nullptr && n_chunks < (1L << 31), "ivit_grad_scale: bad chunk table");
+  IVIT_CHECK_ARG(((uintptr_t)chunks & 7) == 0, "ivit_grad_scale: misaligned chunk table");
+  IVIT_CHECK_ARG(coef != nullptr, "ivit_grad_scale: coef is null");
+  hipLaunchKernelGGL(grad_scale_kernel, dim3((unsigned)n_chunks), dim3(256), 0, ivit_stream(stream), grads, sizes,
+                     (const int2*)chunks, coef);
   IVIT_LAUNCH_CHECK();
   return 0;
 }

@@ -8,12 +8,14 @@ import math
 import torch
 
 import ops
-from _lib import lib, ptr, stream
+from _lib import lib, ptr, stream, workspace
 
 
-class FusedAdamW(torch.optim.Optimizer):
-    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2):
-        super().__init__(params, dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay))
+class _Tables:
+    """Cached device tables of a tensor list (pointers, sizes, (tensor, chunk) records): what the
+    chunked launches (ivit_adamw_chunked, ivit_grad_norm, ivit_grad_scale) take."""
+
+    def __init__(self):
         self._tables = {}
 
     def _table(self, tensors, device):
@@ -28,9 +30,88 @@ class FusedAdamW(torch.optim.Optimizer):
             self._tables[key] = tab
         return tab
 
+    def _table_chunks(self, ps, device):
+        """Device int32 [n][2] table of (tensor, chunk) for ivit_adamw_chunked: every
+        ivit_adamw_chunk_elems()-element chunk of every tensor of the launch."""
+        key = ("chunks",) + tuple(p.numel() for p in ps)
+        tab = self._tables.get(key)
+        if tab is None:
+            ce = lib.ivit_adamw_chunk_elems()
+            rec = [(t, c) for t, p in enumerate(ps) for c in range(-(-p.numel() // ce))]
+            tab = (torch.tensor(rec, dtype=torch.int32).reshape(len(rec), 2).pin_memory().to(device, non_blocking=True),
+                   len(rec))
+            if len(self._tables) > 64:
+                self._tables.clear()
+            self._tables[key] = tab
+        return tab
+
+    def _table_sizes(self, ps, device):
+        key = ("sizes",) + tuple(p.numel() for p in ps)
+        tab = self._tables.get(key)
+        if tab is None:
+            tab = torch.tensor([p.numel() for p in ps], dtype=torch.int64).pin_memory().to(device, non_blocking=True)
+            self._tables[key] = tab
+        return tab
+
+    def _norm_launch(self, grads, max_norm, finite, stats):
+        """ivit_grad_norm over ``grads`` (device f32, contiguous) -> GradNorm; no host read."""
+        max_norm = float(max_norm)
+        if not max_norm > 0.0:
+            raise ValueError(f"max_norm must be > 0 (got {max_norm})")
+        for g in grads:
+            if not g.is_cuda:
+                raise RuntimeError("ivit ops take device tensors (no CPU fallback)")
+            if g.dtype != torch.float32 or not g.is_contiguous():
+                raise TypeError("grad norm: contiguous f32 gradients required")
+        if stats is not None and (stats.dtype != torch.float64 or stats.numel() < 5):
+            raise TypeError("grad norm: stats is a device f64 tensor of 5 elements")
+        dev = grads[0].device if grads else (finite.device if finite is not None else torch.device("cuda"))
+        chunks, nch = self._table_chunks(grads, dev)
+        key = ("normws", nch, str(dev))
+        ws = self._tables.get(key)
+        if ws is None:
+            ws = self._tables[key] = workspace(lib.ivit_grad_norm_workspace(nch), dev)
+        rec = torch.empty(4, dtype=torch.float32, device=dev)  # a fresh record: it outlives later steps
+        tg, sizes = (self._table(grads, dev), self._table_sizes(grads, dev)) if grads else (None, None)
+        lib.ivit_grad_norm(len(grads), ptr(tg), ptr(sizes), ptr(chunks) if nch else None, nch, max_norm, ptr(finite),
+                           ptr(ws), ws.numel(), ptr(rec), ptr(stats), stream())
+        return GradNorm(rec)
+
+    def _scale_launch(self, grads, coef):
+        """ivit_grad_scale: g *= coef (device scalar) in place over ``grads``."""
+        if not grads:
+            return
+        dev = grads[0].device
+        chunks, nch = self._table_chunks(grads, dev)
+        lib.ivit_grad_scale(len(grads), ptr(self._table(grads, dev)), ptr(self._table_sizes(grads, dev)),
+                            ptr(chunks) if nch else None, nch, ptr(coef), stream())
+
+
+class GradNorm:
+    """The device record of one ivit_grad_norm call: ``norm`` (the global L2 norm before clipping),
+    ``coef`` (min(1, max_norm / (norm + 1e-6)), 1 when the norm is not finite) and ``finite`` (1.0 /
+    0.0: the incoming flag and a finite norm), each a 0-d f32 view of ``record``."""
+    __slots__ = ("record", "norm", "coef", "finite")
+
+    def __init__(self, record):
+        self.record = record
+        self.norm, self.coef, self.finite = record[0], record[1], record[2]
+
+
+STATS_FIELDS = ("steps", "clipped", "nonfinite", "norm_sum", "norm_max")  # ivit_grad_norm's stats (f64 [5])
+
+
+class FusedAdamW(torch.optim.Optimizer, _Tables):
+    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2):
+        super().__init__(params, dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay))
+        self._tables = {}
+
     @torch.no_grad()
-    def step(self, closure=None, finite=None):
-        """One AdamW update. ``finite``: optional device scalar (f32); when it holds 0 the launch
+    def step(self, closure=None, finite=None, grad_scale=None):
+        """One AdamW update. ``grad_scale``: optional device scalar (f32, e.g. ``grad_norm(...).coef``);
+        every gradient element is multiplied by it as the launch loads it (``.grad`` stays as it is):
+        the update of ``clip_grad_norm_`` + ``step`` without the pass that rewrites the gradients.
+        ``finite``: optional device scalar (f32); when it holds 0 the launch
         updates nothing — the guard of loss.py:190-198 without a host sync (trainer.Trainer passes
         the loss's flag when it does not sync). On that path the step counts live on the device
         (``state['step']`` is a 0-d f32 device tensor, as torch's capturable AdamW keeps it) and a
@@ -57,13 +138,22 @@ class FusedAdamW(torch.optim.Optimizer):
                     by_step.setdefault(st["step"], []).append(p)
                 for step, ps in by_step.items():
                     b1, b2 = group["betas"]
-                    self._launch(group, ps, 1.0 - b1 ** step, math.sqrt(1.0 - b2 ** step), None, None, None)
+                    self._launch(group, ps, 1.0 - b1 ** step, math.sqrt(1.0 - b2 ** step), None, None, None, grad_scale)
             else:
                 sin, sout = self._device_steps(live)
-                self._launch(group, live, 1.0, 1.0, finite, sin, sout)
+                self._launch(group, live, 1.0, 1.0, finite, sin, sout, grad_scale)
                 for i, p in enumerate(live):
                     self.state[p]["step"] = sout[i]  # 0-d view; the other buffer is next step's output
         return loss
+
+    @torch.no_grad()
+    def grad_norm(self, max_norm, finite=None, stats=None):
+        """Global L2 norm of the live gradients of ALL parameter groups (ivit_grad_norm: two launches,
+        f64 sums, no host read) -> GradNorm (``norm``, ``coef``, ``finite`` as 0-d device views).
+        ``finite``: optional device flag folded into the record's (the loss guard); ``stats``:
+        optional device f64 [5] accumulator (STATS_FIELDS). Pass ``coef`` and ``finite`` to ``step``."""
+        grads = [p.grad for g in self.param_groups for p in g["params"] if p.grad is not None]
+        return self._norm_launch(grads, max_norm, finite, stats)
 
     def _device_steps(self, ps):
         """(steps_in, steps_out) device f32 buffers for this parameter list: steps_in holds every
@@ -85,7 +175,7 @@ class FusedAdamW(torch.optim.Optimizer):
         self._tables[key] = bufs
         return bufs
 
-    def _launch(self, group, ps, bc1, bc2s, finite, sin, sout):
+    def _launch(self, group, ps, bc1, bc2s, finite, sin, sout, grad_scale=None):
         """The update of ``ps`` through the chunked streaming kernel (live bf16 compute copies,
         ops.cast_weight, rewritten in it), then every live row-panel weight pack (ops.packed_weight /
         packed_weight_t) rebuilt from the updated f32 weights in ONE launch: the pointer-table update
@@ -109,9 +199,13 @@ class FusedAdamW(torch.optim.Optimizer):
                     jobs.append((p.data_ptr(), pack.data_ptr(), rows, cols, tr))
                     big = max(big, rows * cols)
         chunks, nch = self._table_chunks(ps, dev)
-        lib.ivit_adamw_chunked(len(ps), ptr(tp), ptr(tg), ptr(tm), ptr(tv), ptr(self._table_ptrs(shadows, dev)),
-                               ptr(sizes), ptr(chunks), nch, group["lr"], b1, b2, group["eps"],
-                               group["weight_decay"], bc1, bc2s, ptr(finite), ptr(sin), ptr(sout), stream())
+        args = (len(ps), ptr(tp), ptr(tg), ptr(tm), ptr(tv), ptr(self._table_ptrs(shadows, dev)), ptr(sizes),
+                ptr(chunks), nch, group["lr"], b1, b2, group["eps"], group["weight_decay"], bc1, bc2s, ptr(finite),
+                ptr(sin), ptr(sout))
+        if grad_scale is None:
+            lib.ivit_adamw_chunked(*args, stream())
+        else:
+            lib.ivit_adamw_chunked_scaled(*args, ptr(grad_scale), stream())
         if jobs:
             lib.ivit_weight_pack_multi(len(jobs), ptr(self._pack_jobs(jobs, dev)), big, stream())
 
@@ -154,25 +248,28 @@ class FusedAdamW(torch.optim.Optimizer):
             self._tables[key] = tab
         return tab
 
-    def _table_chunks(self, ps, device):
-        """Device int32 [n][2] table of (tensor, chunk) for ivit_adamw_chunked: every
-        ivit_adamw_chunk_elems()-element chunk of every tensor of the launch."""
-        key = ("chunks",) + tuple(p.numel() for p in ps)
-        tab = self._tables.get(key)
-        if tab is None:
-            ce = lib.ivit_adamw_chunk_elems()
-            rec = [(t, c) for t, p in enumerate(ps) for c in range(-(-p.numel() // ce))]
-            tab = (torch.tensor(rec, dtype=torch.int32).reshape(-1, 2).pin_memory().to(device, non_blocking=True),
-                   len(rec))
-            if len(self._tables) > 64:
-                self._tables.clear()
-            self._tables[key] = tab
-        return tab
 
-    def _table_sizes(self, ps, device):
-        key = ("sizes",) + tuple(p.numel() for p in ps)
-        tab = self._tables.get(key)
-        if tab is None:
-            tab = torch.tensor([p.numel() for p in ps], dtype=torch.int64).pin_memory().to(device, non_blocking=True)
-            self._tables[key] = tab
-        return tab
+_clip_tables = _Tables()
+
+
+@torch.no_grad()
+def clip_grad_norm_(parameters, max_norm, norm_type=2.0, error_if_nonfinite=False):
+    """torch.nn.utils.clip_grad_norm_ (L2 only) on the device: ivit_grad_norm then ivit_grad_scale, no
+    host read; returns the total norm before clipping as a 0-d device tensor. The norm is summed in
+    f64 and does not depend on the gradients' layout. A non-finite norm leaves the gradients as they
+    are (torch would multiply them by a NaN coefficient); ``error_if_nonfinite=True`` costs one host
+    read and raises as torch does."""
+    if float(norm_type) != 2.0:
+        raise ValueError(f"clip_grad_norm_: only norm_type 2 is built (got {norm_type})")
+    if isinstance(parameters, torch.Tensor):
+        parameters = [parameters]
+    grads = [p.grad for p in parameters if p.grad is not None]
+    if not grads:
+        return torch.tensor(0.0)
+    rec = _clip_tables._norm_launch(grads, max_norm, None, None)
+    if error_if_nonfinite and not bool(torch.isfinite(rec.norm)):
+        raise RuntimeError(f"The total norm of order {float(norm_type)} for gradients from `parameters` is "
+                           "non-finite, so it cannot be clipped. To disable this error and scale the gradients "
+                           "by the non-finite norm anyway, set `error_if_nonfinite=False`")
+    _clip_tables._scale_launch(grads, rec.coef)
+    return rec.norm

@@ -11,6 +11,8 @@ sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 
 import train_vit  # noqa: E402
 
+parse_args = train_vit.parse_args  # the shared parser (--clip-grad-norm included)
+
 
 def main(argv=None):
     return train_vit.main(argv, variant="cnn")

@@ -16,6 +16,8 @@ same per-batch NaN skips and the same checkpoint dict ({'epoch', 'model_state_di
   shard 1234 + r; only rank 0 prints and saves;
 * the optimizer is FusedAdamW (same AdamW update, one launch per step); ``--dtype bf16`` runs
   the kernels in bf16 with f32 master weights, ``fp32`` is the parity setting;
+* ``--clip-grad-norm X`` bounds the global gradient norm (trainer.Trainer ``max_grad_norm``); the
+  epoch line then reports the mean and max norm and the clipped / skipped steps (one host read);
 * the reference's import-time defects (train_vit.py:34-35 undefined LIDAR_TOTAL_CHANNELS /
   MAP_CHANNELS, :131 ``verbose``) are fixed without changing any value.
 """
@@ -27,8 +29,8 @@ from pathlib import Path
 
 import torch
 
-from constants import (ANCHOR_CONFIGS_PAPER, DOMINANT_CLASSES_FOR_DOWNSAMPLING, GRID_HEIGHT_PX, GRID_WIDTH_PX,
-                       INTENTION_DOWNSAMPLE_RATIO, LIDAR_SWEEPS, LIDAR_TOTAL_CHANNELS, MAP_CHANNELS)
+from constants import (ANCHOR_CONFIGS_PAPER, DOMINANT_CLASSES_FOR_DOWNSAMPLING, GRAD_CLIP_NORM, GRID_HEIGHT_PX,
+                       GRID_WIDTH_PX, INTENTION_DOWNSAMPLE_RATIO, LIDAR_SWEEPS, LIDAR_TOTAL_CHANNELS, MAP_CHANNELS)
 from ddp import all_reduce_sum, any_rank, init_distributed
 from loss import DetectionIntentionLoss
 from model_vit import BasicBlock, IntentNetViT
@@ -102,7 +104,18 @@ def parse_args(argv=None):
     ap.add_argument("--fresh-batches", action="store_true", help="draw a new synthetic batch every step")
     ap.add_argument("--augment", action="store_true",
                     help="training-time augment_bev on every batch (dataset.py:352-353), on the GPU")
+    ap.add_argument("--clip-grad-norm", type=float, default=GRAD_CLIP_NORM, metavar="X",
+                    help="clip the global gradient L2 norm to X on the device (no host sync); a non-finite "
+                         "gradient norm skips the update")
     return ap.parse_args(argv)
+
+
+def grad_clip_line(st, max_norm):
+    """The epoch's gradient-norm report from Trainer.grad_stats() (the norms are the same on every rank)."""
+    ok = st["steps"] - st["nonfinite"]
+    mean = st["norm_sum"] / ok if ok > 0 else float("nan")
+    return (f"  Grad norm (clip {max_norm:g}): mean {mean:.4g}, max {st['norm_max']:.4g}, "
+            f"clipped {int(st['clipped'])}/{int(st['steps'])} steps, skipped {int(st['nonfinite'])} (non-finite)")
 
 
 def _in_lockstep(loader, device):
@@ -178,7 +191,8 @@ def main(argv=None, variant="vit"):
     scheduler = torch.optim.lr_scheduler.ReduceLROnPlateau(optimizer, mode='min', factor=0.1, patience=3)
     anchors = generate_anchors(H, W, stride, ANCHOR_CONFIGS_PAPER, device=device)
     log(f"Anchors generated (stride {stride}), shape: {tuple(anchors.shape)}")
-    trainer = Trainer(model, loss_fn, optimizer, anchors, world=world, bucket_mb=args.bucket_mb, check_nan=True)
+    trainer = Trainer(model, loss_fn, optimizer, anchors, world=world, bucket_mb=args.bucket_mb, check_nan=True,
+                      max_grad_norm=args.clip_grad_norm)
 
     log(f"\n--- Starting {tag} Training ---")
     for epoch in range(args.epochs):
@@ -204,6 +218,9 @@ def main(argv=None, variant="vit"):
             log(f"Epoch {epoch + 1} Summary: Avg Loss: {avg[0]:.4f} (Cls: {avg[1]:.4f}, Box: {avg[2]:.4f}, "
                 f"Intent: {avg[3]:.4f}) LR: {optimizer.param_groups[0]['lr']:.1e}  "
                 f"[{n_ok * args.batch / dt:.1f} samples/s]")
+            if args.clip_grad_norm is not None:
+                log(grad_clip_line(trainer.grad_stats(), args.clip_grad_norm))
+                trainer.reset_grad_stats()
             scheduler.step(avg[0])
         else:
             log(f"Epoch {epoch + 1} Warning: No batches processed successfully.")

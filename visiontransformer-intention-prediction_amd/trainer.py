@@ -19,6 +19,15 @@ checks do; the benchmark turns them off (``check_nan=False``) — nothing else i
 the host checks a non-finite loss still zeroes the update: backward runs (exact-zero gradients
 from the loss kernel) and FusedAdamW's launch reads the loss's device finite flag (min over ranks
 under DDP) and leaves weights and moments untouched; only its host step counters advance.
+
+``max_grad_norm`` (None = off, exactly the step above): global L2-norm clipping without a host
+read. After ``buckets.finish()`` the gradients are final (and bit-identical on every rank, so the
+norm needs no collective); FusedAdamW.grad_norm takes their norm (f64 sums, a fixed order), and the
+update launch multiplies each gradient by the clip coefficient as it loads it and reads
+``finite = loss flag AND norm finite``: a gradient that overflowed skips the update like a
+non-finite loss does (weights, moments and device step counts unchanged). The loss dict gains
+``grad_norm`` (the norm before clipping, a 0-d device tensor); ``clipped`` / ``nonfinite_grad`` /
+``grad_stats()`` read the device accumulator on demand.
 """
 from __future__ import annotations
 
@@ -26,12 +35,19 @@ import torch
 
 from ddp import GradBuckets, any_rank, broadcast_state, grad_order, min_on_device
 from loss import device_guard
-from optim import FusedAdamW
+from optim import STATS_FIELDS, FusedAdamW
 
 
 class Trainer:
     def __init__(self, model, loss_fn, optimizer, anchors, world: int = 1, bucket_mb: float = 64.0,
-                 check_nan: bool = True, force_buckets: bool = False):
+                 check_nan: bool = True, force_buckets: bool = False, max_grad_norm: float | None = None):
+        if max_grad_norm is not None:
+            if not float(max_grad_norm) > 0.0:
+                raise ValueError(f"Trainer: max_grad_norm must be > 0 or None (got {max_grad_norm})")
+            if not isinstance(optimizer, FusedAdamW):
+                raise TypeError("Trainer: max_grad_norm needs FusedAdamW (the clip is part of its launch)")
+        self.max_grad_norm = None if max_grad_norm is None else float(max_grad_norm)
+        self._grad_stats = None  # device f64 [5], optim.STATS_FIELDS
         self.model, self.loss_fn, self.optimizer, self.anchors = model, loss_fn, optimizer, anchors
         self.world = world
         self.check_nan = check_nan
@@ -51,6 +67,25 @@ class Trainer:
             self.buckets.zero_grad()
         else:
             self.optimizer.zero_grad(set_to_none=True)
+
+    def grad_stats(self):
+        """{steps, clipped, nonfinite, norm_sum, norm_max} of the clipped steps so far: ONE host read."""
+        vals = self._grad_stats.tolist() if self._grad_stats is not None else [0.0] * len(STATS_FIELDS)
+        return dict(zip(STATS_FIELDS, vals))
+
+    def reset_grad_stats(self):
+        if self._grad_stats is not None:
+            self._grad_stats.zero_()
+
+    @property
+    def clipped(self):
+        """Steps whose gradient norm exceeded max_grad_norm (a host read)."""
+        return int(self.grad_stats()["clipped"])
+
+    @property
+    def nonfinite_grad(self):
+        """Steps skipped because the gradient norm was not finite (a host read)."""
+        return int(self.grad_stats()["nonfinite"])
 
     def _loss_finite(self, d):
         fin = getattr(self.loss_fn, "last_finite", None)
@@ -78,7 +113,16 @@ class Trainer:
         if self.buckets is not None:
             self.buckets.finish()
         fin = getattr(self.loss_fn, "last_finite", None)
-        if not self.check_nan and fin is not None and isinstance(self.optimizer, FusedAdamW):
+        if self.max_grad_norm is not None:
+            # with the host checks on, every rank has already agreed that the loss is finite
+            if not self.check_nan and fin is not None and self.buckets is not None and self.world > 1:
+                fin = min_on_device(fin)
+            if self._grad_stats is None:
+                self._grad_stats = torch.zeros(len(STATS_FIELDS), dtype=torch.float64, device=dev)
+            gn = self.optimizer.grad_norm(self.max_grad_norm, finite=fin, stats=self._grad_stats)
+            self.optimizer.step(finite=gn.finite, grad_scale=gn.coef)
+            d["grad_norm"] = gn.norm
+        elif not self.check_nan and fin is not None and isinstance(self.optimizer, FusedAdamW):
             # no host sync: the update launch itself reads the loss's finite flag and does nothing
             # on 0 (weights and moments unchanged, as with the reference's disconnected zero loss)
             if self.buckets is not None and self.world > 1:
