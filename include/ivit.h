@@ -205,7 +205,8 @@ int ivit_unpack_conv_grad(const float* gp, long Cout, long Cin, long ks, float* 
  *      constants and a prescaled Q copy). IVIT_F32, the exact parity path, materialises the scores:
  *      its workspace is 4 B*H*N*ldS bytes (ldS >= N; twice that for the backward) — 0.49 GB per
  *      sample at N = 4501, H = 6, and 7.8 GB at N = 18 001: sized for the parity tests and
- *      config 1 (B = 1), not for training at scale.                                           */
+ *      config 1 (B = 1), not for training at scale. Its backward recomputes P as a softmax of
+ *      the recomputed scores (rows normalised by their own sum) and does not read lse.       */
 long ivit_attn_workspace(int dtype, long B, long N, long H, long Dh, int backward);
 int ivit_attn_fwd(int dtype, const void* qkv, long B, long N, long H, long Dh, void* out, float* lse, void* work,
                   long work_bytes, void* stream);

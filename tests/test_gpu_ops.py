@@ -180,6 +180,14 @@ def test_attention_q2_prescaled_path(B, N, H):
     assert _rel(o.float(), oref.detach()) < 2e-2
     # the extra bf16 rounding of q * c (the f32 test rounds q once); few rows: a single score's rounding
     assert _rel(lse, lref.detach()) < (6e-4 if N >= 64 else 3e-3)
+    if N <= 449:
+        # per element, against f64 on the rounded qs the kernel reads (tests/attn_cases.py's bounds):
+        # one wrong row or 16-key block of small entries does not fit under these
+        import attn_cases as AC
+        for z in range(B * H):
+            r = AC.fwd_ratios(AC.slot_rows(o, B, N, H, z), lse.reshape(B * H, N)[z].cpu(),
+                              AC.fwd_ref(*AC.slot_qkv(qs, B, N, H, z)))
+            AC.assert_ratios(r, f"slot {z}")
     dod = ops.cast(torch.randn(B * N, D).to(DEV), torch.bfloat16)
     oref.backward(dod.float().cpu().double())
     dq = ops.attn_bwd_q2(qs, o, dod, lse, B, N, H)

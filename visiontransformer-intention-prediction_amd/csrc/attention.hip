@@ -986,7 +986,8 @@ __global__ __launch_bounds__(64 * W, 8 / W) void attn_bwd_dq_v4_kernel(const bf1
 }
 
 // ------------------------------------------------------------------------- f32 row kernels
-// S rows (already scaled) -> P = softmax, zero padding columns; lse = max + log(sum).
+// S rows (already scaled) -> P = softmax, zero padding columns; lse = max + log(sum) (null: not
+// written, the backward's recompute).
 __global__ void softmax_rows_kernel(float* __restrict__ S, long ldS, int N, float* __restrict__ lse) {
   const long row = blockIdx.x;  // z * N + q
   float* s = S + row * ldS;
@@ -1010,15 +1011,7 @@ __global__ void softmax_rows_kernel(float* __restrict__ S, long ldS, int N, floa
   sum = red[0] + red[1] + red[2] + red[3];
   const float inv = 1.f / sum;
   for (int i = threadIdx.x; i < ldS; i += 256) s[i] = i < N ? s[i] * inv : 0.f;
-  if (threadIdx.x == 0) lse[row] = mx + logf(sum);
-}
-
-// P = exp(S - lse) (recompute in backward), zero padding.
-__global__ void prob_rows_kernel(float* __restrict__ S, long ldS, int N, const float* __restrict__ lse) {
-  const long row = blockIdx.x;
-  float* s = S + row * ldS;
-  const float l = lse[row];
-  for (int i = threadIdx.x; i < ldS; i += 256) s[i] = i < N ? expf(s[i] - l) : 0.f;
+  if (threadIdx.x == 0 && lse) lse[row] = mx + logf(sum);
 }
 
 // dS = P * (dP - rowsum(P * dP)) in place of dP.
@@ -1179,13 +1172,15 @@ extern "C" int ivit_attn_bwd(int dtype, const void* qkv, const void* out, const 
   float* dq = (float*)dqkv;
   const int Z = (int)(B * H);
   const BatchOff qoff{H, N * ldq, Dh}, soff{1, zs, 0}, ooff{H, N * D, Dh};
-  // recompute P
+  // recompute P as the forward did, rows normalised by their own sum: exp(S - lse) on the f32 lse
+  // is off by |lse| ulps of f32 in every P, so a row no longer sums to 1 and dS = P (dP - sum P dP)
+  // of a one-hot row, where the two terms cancel, carried that error times dP
   {
     LdDense<float> la{Q, ldq, (int)N, (int)Dh, 0, 0, 0, qoff};
     LdDense<float> lb{Q + D, ldq, (int)N, (int)Dh, 0, 0, 0, qoff};
     EpiStore<float> es{P, ldS, soff, nullptr, IVIT_ACT_NONE, nullptr, scale};
     launch_gemm<true, true>(false, la, lb, es, (int)N, (int)N, (int)Dh, Z, 1, st);
-    hipLaunchKernelGGL(prob_rows_kernel, dim3(Z * N), dim3(256), 0, st, P, ldS, (int)N, lse);
+    hipLaunchKernelGGL(softmax_rows_kernel, dim3(Z * N), dim3(256), 0, st, P, ldS, (int)N, (float*)nullptr);
   }
   // dV = P^T dO
   {
