@@ -413,6 +413,35 @@ int ivit_det_match(const float* iou, const long* iou_off, const int* npred, cons
                    long n_samples, long total_pred, const float* thresholds, long n_thr, double* ap, int* best_gt,
                    unsigned char* tp, void* work, long work_bytes, int max_gt, void* stream);
 
+/* ---- Detection error breakdown (extends eval_vit.py:191-292: the same matching, then why a
+ * prediction or a GT did not count; the reference's "detailed error analysis" future work).
+ * iou / iou_off / npred / ngt / pred_off as ivit_det_match; sample s's GTs occupy gt_off[s] ..
+ * gt_off[s] + ngt[s] - 1 of gt_boxes / gt_int / gt_status. pred_boxes [total_pred, 5] f32 in score
+ * order, gt_boxes [total_gt, 5] f32, both (cx, cy, w, l, yaw) in ego-centric metres; pred_int /
+ * gt_int int32 intentions. range_edges: n_edges <= 7 ascending f32 in HOST memory (read before
+ * the launch): bin b holds edges[b-1] <= r < edges[b], nb = n_edges + 1 bins. Outputs:
+ *   category [total_pred] u8: 0 TP, 1 DUP (best >= thr_fg, not the first of its GT), 2 LOC
+ *     (thr_bg <= best < thr_fg), 3 BKG (best < thr_bg, or the sample has no GT);
+ *   gt_status [total_gt] u8: 0 MATCHED, 1 MISSED_NEAR (column max >= thr_bg), 2 MISSED_NONE;
+ *   best_gt [total_pred] int32 (first-max GT, -1 without GTs);
+ *   errors [total_pred, 4] f64: ate, ase, aoe, aoe_pi of a TP against its GT, 0 elsewhere;
+ *   tallies [n_samples, nb, 12] f64: counts TP DUP LOC BKG MISSED_NEAR MISSED_NONE GT, sums ate ase
+ *     aoe aoe_pi over TPs, TPs whose intention lies outside 0..7 (a TP and a GT are binned by the
+ *     GT's centre, every other prediction by its own);
+ *   confusion [n_samples, nb, 8, 8] int32 over TPs: GT intention row, predicted intention column;
+ *   ap [n_samples, 5] f64: base, no_dup, no_bkg, fix_loc, no_miss (the AP of ivit_det_match over
+ *     the variant's kept predictions and GT count; base equals ivit_det_match at thr_fg).
+ * Integer LDS atomics and fixed-order f64 sums only: the same input gives the same bits.
+ * work >= ivit_det_errors_workspace(n_samples, total_pred) bytes; max_gt <= 4096;
+ * 0 <= thr_bg < thr_fg.                                                                        */
+long ivit_det_errors_workspace(long n_samples, long total_pred);
+int ivit_det_errors(const float* iou, const long* iou_off, const int* npred, const int* ngt, const long* pred_off,
+                    const long* gt_off, long n_samples, long total_pred, const float* pred_boxes,
+                    const float* gt_boxes, const int* pred_int, const int* gt_int, float thr_fg, float thr_bg,
+                    const float* range_edges, int n_edges, unsigned char* category, unsigned char* gt_status,
+                    int* best_gt, double* errors, double* tallies, int* confusion, double* ap, void* work,
+                    long work_bytes, int max_gt, void* stream);
+
 /* ---- LiDAR BEV voxelisation ----------------------------------------
  * Replaces utils.create_intentnet_lidar_bev (utils.py:62-106) and, when sweep_tf is given, the
  * per-sweep transform_points(pts, rel_tf) of dataset.py:319-340 (utils.py:27-33) in one pass.

@@ -18,6 +18,14 @@ makes the NMS suppress on the rotated IoU of the decoded boxes instead of their 
 ``--attn-maps DIR`` (the reference's other future-work item, qualitative analysis of the attention)
 writes, per batch, the attention maps of both ViT streams for each sample's ``--attn-top`` best
 detections at ``--attn-blocks`` (AttnDump; IntentNetViT.attention_maps).
+``--error-report PATH`` (the reference's "detailed error analysis" future-work item) says where the
+mAP is lost: after the intention block it prints, per range bin from the ego vehicle
+(``--error-range-edges``), how many detections at ``--error-iou`` are true positives, duplicates,
+mislocalised (best IoU between ``--error-bg-iou`` and ``--error-iou``) or background, how many GTs
+were missed with and without a detection nearby, the translation / scale / orientation error of the
+true positives and the mAP each error type costs, and writes the same numbers to PATH as JSON
+(metrics.error_analysis, ivit_det_errors: all samples in one launch; ``--rotated`` picks the IoU).
+Without the flag the output is unchanged.
 """
 from __future__ import annotations
 
@@ -90,6 +98,14 @@ def parse_args(argv=None):
     ap.add_argument("--attn-top", type=int, default=8, help="detections per sample (highest score after NMS)")
     ap.add_argument("--attn-blocks", type=str, default="-1",
                     help="comma list of ViT block indices, negative from the end")
+    ap.add_argument("--error-report", type=str, default=None, metavar="PATH",
+                    help="write the detection error breakdown (metrics.error_analysis) as JSON and print its table")
+    ap.add_argument("--error-iou", type=float, default=IOU_THRESHOLD_FOR_INTENTION_MATCH,
+                    help="IoU a detection needs to count in the error breakdown")
+    ap.add_argument("--error-bg-iou", type=float, default=0.1,
+                    help="best IoU below which a detection is background, not a localisation error")
+    ap.add_argument("--error-range-edges", type=str, default="20,40,60",
+                    help="comma list of range-bin edges in metres from the ego vehicle (ascending, at most 7)")
     return ap.parse_args(argv)
 
 
@@ -262,6 +278,15 @@ def main_eval_vit(argv=None, variant="vit"):
     else:
         print(f"\nNo True Positive detections found for {tag} model at IoU >= {IOU_THRESHOLD_FOR_INTENTION_MATCH} "
               "to evaluate intention.")
+    if args.error_report is not None:
+        from metrics import error_analysis, error_report_json, format_error_report
+        edges = [float(e) for e in args.error_range_edges.split(",") if e.strip()]
+        report = error_analysis(results, args.error_iou, args.error_bg_iou, args.rotated, edges)
+        print(f"\n--- {tag} Detection Error Breakdown ---")
+        print(format_error_report(report))
+        with open(args.error_report, "w") as f:
+            f.write(error_report_json(report) + "\n")
+        print(f"Error report written to {args.error_report}")
     print(f"\n--- Evaluation Script for {tag} Finished ---")
     return 0
 
