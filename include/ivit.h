@@ -350,6 +350,26 @@ int ivit_adamw_chunked_scaled(long n_tensors, void* const* params, void* const* 
                               long n_chunks, float lr, double beta1, double beta2, float eps, float weight_decay,
                               float bc1, float bc2_sqrt, const float* finite, const float* steps_in,
                               float* steps_out, const float* grad_scale, void* stream);
+/* ivit_adamw_chunked_scaled that also moves an exponential moving average of the weights, in the
+ * same launch: emas (device table of f32 pointers; null = ivit_adamw_chunked_scaled, bit-identical;
+ * a null entry = that tensor is not averaged) and, after the parameter update,
+ *   e = e + omd * (p_new - e)   in f32: one subtract, one multiply, one add, never fused
+ *   omd = (float)(1.0 - d),  d = ema_warmup ? min(ema_decay, (1 + n) / (10 + n)) : ema_decay   in f64
+ * with n = steps_in[t] + 1, the tensor's step count after this update. ema_warmup therefore needs
+ * steps_in; a caller that counts on the host passes that step's d as ema_decay with ema_warmup 0.
+ * finite = 0 writes nothing, e included. grad_scale null = no gradient multiply. ema_decay must be
+ * in [0, 1). */
+int ivit_adamw_chunked_ema(long n_tensors, void* const* params, void* const* grads, void* const* exp_avg,
+                           void* const* exp_avg_sq, void* const* shadows, const long* sizes, const int* chunks,
+                           long n_chunks, float lr, double beta1, double beta2, float eps, float weight_decay,
+                           float bc1, float bc2_sqrt, const float* finite, const float* steps_in, float* steps_out,
+                           const float* grad_scale, void* const* emas, double ema_decay, int ema_warmup,
+                           void* stream);
+/* a[t] <-> b[t] (f32, sizes[t] elements) exchanged in place over the same chunk grid, no third
+ * buffer; shadows (may be null or hold null entries) receives bf16 of the new a[t]. Puts the averaged
+ * weights into the model and back (optim.ModelEMA.swapped). */
+int ivit_swap_chunked(long n_tensors, void* const* a, void* const* b, const long* sizes, const int* chunks,
+                      long n_chunks, void* const* shadows, void* stream);
 
 /* ---- Global gradient norm / clipping (torch.nn.utils.clip_grad_norm_, norm_type 2). ---------- */
 /* L2 norm over n_tensors f32 tensors given as ivit_adamw_chunked takes them (pointer table, sizes,

@@ -183,22 +183,39 @@ __global__ __launch_bounds__(256) void adamw_kernel(void* const* params, void* c
 // SCALED (ivit_adamw_chunked_scaled): every gradient element is first multiplied by *grad_scale (the
 // clip coefficient of ivit_grad_norm) — the product ivit_grad_scale would have stored, so the fused and
 // the unfused form give the same bits. The unscaled instantiation is the kernel as it was.
+// EMA (ivit_adamw_chunked_ema): emas[t] (f32, null per tensor = not averaged) is the tensor's
+// exponential moving average, moved towards the parameter this launch has just computed and still
+// holds in a register: e += omd * (p_new - e), three f32 operations with contraction off, so a host
+// that repeats them on the stored weights gets the same bits. omd = (float)(1 - d) with d in f64,
+// formed once per workgroup before the element loop: d = ema_decay, or under ema_warmup
+// min(ema_decay, (1 + n) / (10 + n)) with n = steps_in[t] + 1, this tensor's count after the update
+// (device counts only: without them the host knows n and passes the step's d as ema_decay). It sits
+// behind the finite exit like the pow of the bias corrections, so a skipped launch pays for neither
+// and leaves e alone. The EMA = false instantiations are the kernels as they were.
 constexpr int AW_CHUNK = 4096;
 IVIT_DEV float scaled_grad(float g, float s) {
 #pragma clang fp contract(off)
   return g * s;
 }
-template <bool SCALED>
+IVIT_DEV float ema_elem(float e, float p, float omd) {
+#pragma clang fp contract(off)
+  const float diff = p - e;
+  const float mv = omd * diff;
+  return e + mv;
+}
+template <bool SCALED, bool EMA>
 __global__ __launch_bounds__(256) void adamw_chunk_kernel(void* const* params, void* const* grads, void* const* ms,
                                                           void* const* vs, const long* sizes, const int2* chunks,
                                                           float lr, float b2, float eps, float wd, float bc1,
                                                           float bc2s, void* const* shadows, const float* finite,
                                                           const float* steps_in, float* steps_out, double b1d,
                                                           double b2d, float omb1, float omb2,
-                                                          const float* grad_scale) {
+                                                          const float* grad_scale, void* const* emas,
+                                                          double ema_decay, int ema_warmup) {
   const int2 ck = chunks[blockIdx.x];
   const int t = ck.x;
   const bool go = finite == nullptr || *finite != 0.f;
+  double nstep = 0.0;  // EMA: the count after this update (device counts)
   if (steps_in != nullptr) {
     const float s0 = steps_in[t];
     if (ck.y == 0 && threadIdx.x == 0) steps_out[t] = go ? s0 + 1.f : s0;
@@ -206,8 +223,18 @@ __global__ __launch_bounds__(256) void adamw_chunk_kernel(void* const* params, v
     const double s = (double)s0 + 1.0;
     bc1 = (float)(1.0 - pow(b1d, s));
     bc2s = (float)sqrt(1.0 - pow(b2d, s));
+    nstep = s;
   }
   if (!go) return;
+  float omd = 0.f;
+  if constexpr (EMA) {
+    double d = ema_decay;
+    if (ema_warmup) {
+      const double w = (1.0 + nstep) / (10.0 + nstep);
+      d = w < d ? w : d;
+    }
+    omd = (float)(1.0 - d);
+  }
   const long off = (long)ck.y * AW_CHUNK;
   const long n = sizes[t];
   const int len = (int)min((long)AW_CHUNK, n - off);
@@ -216,6 +243,8 @@ __global__ __launch_bounds__(256) void adamw_chunk_kernel(void* const* params, v
   float* m = (float*)ms[t] + off;
   float* v = (float*)vs[t] + off;
   bf16* sh = shadows && shadows[t] ? (bf16*)shadows[t] + off : nullptr;
+  float* ea = nullptr;
+  if constexpr (EMA) ea = emas[t] ? (float*)emas[t] + off : nullptr;
   const float step = lr / bc1, keep = 1.f - lr * wd;
   float gs = 1.f;
   if constexpr (SCALED) gs = *grad_scale;
@@ -224,7 +253,7 @@ __global__ __launch_bounds__(256) void adamw_chunk_kernel(void* const* params, v
     adamw_elem(gi, pi, mi, vi, keep, omb1, b2, omb2, bc2s, eps, step);
   };
   const bool vec = ((((uintptr_t)p | (uintptr_t)g | (uintptr_t)m | (uintptr_t)v) & 15) == 0) &&
-                   (((uintptr_t)sh & 7) == 0) && (len & 3) == 0;
+                   (((uintptr_t)sh & 7) == 0) && (((uintptr_t)ea & 15) == 0) && (len & 3) == 0;
   if (vec) {
     for (int i = threadIdx.x * 4; i < len; i += 1024) {
       const float4 gi = *(const float4*)(g + i);
@@ -237,6 +266,16 @@ __global__ __launch_bounds__(256) void adamw_chunk_kernel(void* const* params, v
       *(float4*)(m + i) = mi;
       *(float4*)(v + i) = vi;
       if (sh) *(uint2*)(sh + i) = make_uint2(pk_bf16(pi.x, pi.y), pk_bf16(pi.z, pi.w));
+      if constexpr (EMA) {
+        if (ea) {
+          float4 ei = *(const float4*)(ea + i);
+          ei.x = ema_elem(ei.x, pi.x, omd);
+          ei.y = ema_elem(ei.y, pi.y, omd);
+          ei.z = ema_elem(ei.z, pi.z, omd);
+          ei.w = ema_elem(ei.w, pi.w, omd);
+          *(float4*)(ea + i) = ei;
+        }
+      }
     }
   } else {
     for (int i = threadIdx.x; i < len; i += 256) {
@@ -246,6 +285,39 @@ __global__ __launch_bounds__(256) void adamw_chunk_kernel(void* const* params, v
       m[i] = mi;
       v[i] = vi;
       if (sh) sh[i] = (bf16)pi;
+      if constexpr (EMA) {
+        if (ea) ea[i] = ema_elem(ea[i], pi, omd);
+      }
+    }
+  }
+}
+
+// a[t] <-> b[t] element by element over the chunk grid (ivit_swap_chunked), each element read into a
+// register and written to the other side: no third buffer. shadows[t] (bf16, null = none) receives
+// the new a, as the update launch writes the new parameter. Same vector / scalar split.
+__global__ __launch_bounds__(256) void swap_chunk_kernel(void* const* as, void* const* bs, const long* sizes,
+                                                         const int2* chunks, void* const* shadows) {
+  const int2 ck = chunks[blockIdx.x];
+  const int t = ck.x;
+  const long off = (long)ck.y * AW_CHUNK;
+  const int len = (int)min((long)AW_CHUNK, sizes[t] - off);
+  float* a = (float*)as[t] + off;
+  float* b = (float*)bs[t] + off;
+  bf16* sh = shadows && shadows[t] ? (bf16*)shadows[t] + off : nullptr;
+  const bool vec = ((((uintptr_t)a | (uintptr_t)b) & 15) == 0) && (((uintptr_t)sh & 7) == 0) && (len & 3) == 0;
+  if (vec) {
+    for (int i = threadIdx.x * 4; i < len; i += 1024) {
+      const float4 ai = *(const float4*)(a + i), bi = *(const float4*)(b + i);
+      *(float4*)(a + i) = bi;
+      *(float4*)(b + i) = ai;
+      if (sh) *(uint2*)(sh + i) = make_uint2(pk_bf16(bi.x, bi.y), pk_bf16(bi.z, bi.w));
+    }
+  } else {
+    for (int i = threadIdx.x; i < len; i += 256) {
+      const float ai = a[i], bi = b[i];
+      a[i] = bi;
+      b[i] = ai;
+      if (sh) sh[i] = (bf16)bi;
     }
   }
 }
@@ -349,7 +421,7 @@ __global__ __launch_bounds__(GN_FINAL) void grad_norm_final_kernel(const double*
 }
 
 // g *= *coef over the chunk grid (the second half of clip_grad_norm_). The products are the ones
-// adamw_chunk_kernel<true> forms in registers. coef == 1 (no clipping) would rewrite every element
+// adamw_chunk_kernel<SCALED = true> forms in registers. coef == 1 (no clipping) would rewrite every element
 // with itself: nothing is stored.
 __global__ __launch_bounds__(256) void grad_scale_kernel(void* const* grads, const long* sizes, const int2* chunks,
                                                          const float* coef) {
@@ -486,10 +558,10 @@ extern "C" int ivit_adamw_chunked(long n_tensors, void* const* params, void* con
   IVIT_CHECK_ARG((steps_in == nullptr) == (steps_out == nullptr), "ivit_adamw_chunked: steps_in / steps_out pair");
   IVIT_CHECK_ARG(steps_in == nullptr || steps_in != steps_out, "ivit_adamw_chunked: steps_out aliases steps_in");
   IVIT_CHECK_ARG(((uintptr_t)chunks & 7) == 0, "ivit_adamw_chunked: misaligned chunk table");
-  hipLaunchKernelGGL(adamw_chunk_kernel<false>, dim3((unsigned)n_chunks), dim3(256), 0, ivit_stream(stream), params,
-                     grads, exp_avg, exp_avg_sq, sizes, (const int2*)chunks, lr, (float)beta2, eps, weight_decay, bc1,
-                     bc2_sqrt, shadows, finite, steps_in, steps_out, beta1, beta2, (float)(1.0 - beta1),
-                     (float)(1.0 - beta2), (const float*)nullptr);
+  hipLaunchKernelGGL((adamw_chunk_kernel<false, false>), dim3((unsigned)n_chunks), dim3(256), 0, ivit_stream(stream),
+                     params, grads, exp_avg, exp_avg_sq, sizes, (const int2*)chunks, lr, (float)beta2, eps,
+                     weight_decay, bc1, bc2_sqrt, shadows, finite, steps_in, steps_out, beta1, beta2,
+                     (float)(1.0 - beta1), (float)(1.0 - beta2), (const float*)nullptr, (void* const*)nullptr, 0.0, 0);
   IVIT_LAUNCH_CHECK();
   return 0;
 }
@@ -509,10 +581,58 @@ extern "C" int ivit_adamw_chunked_scaled(long n_tensors, void* const* params, vo
                  "ivit_adamw_chunked_scaled: steps_in / steps_out pair");
   IVIT_CHECK_ARG(steps_in == nullptr || steps_in != steps_out, "ivit_adamw_chunked_scaled: steps_out aliases steps_in");
   IVIT_CHECK_ARG(((uintptr_t)chunks & 7) == 0, "ivit_adamw_chunked_scaled: misaligned chunk table");
-  hipLaunchKernelGGL(adamw_chunk_kernel<true>, dim3((unsigned)n_chunks), dim3(256), 0, ivit_stream(stream), params,
-                     grads, exp_avg, exp_avg_sq, sizes, (const int2*)chunks, lr, (float)beta2, eps, weight_decay, bc1,
-                     bc2_sqrt, shadows, finite, steps_in, steps_out, beta1, beta2, (float)(1.0 - beta1),
-                     (float)(1.0 - beta2), grad_scale);
+  hipLaunchKernelGGL((adamw_chunk_kernel<true, false>), dim3((unsigned)n_chunks), dim3(256), 0, ivit_stream(stream),
+                     params, grads, exp_avg, exp_avg_sq, sizes, (const int2*)chunks, lr, (float)beta2, eps,
+                     weight_decay, bc1, bc2_sqrt, shadows, finite, steps_in, steps_out, beta1, beta2,
+                     (float)(1.0 - beta1), (float)(1.0 - beta2), grad_scale, (void* const*)nullptr, 0.0, 0);
+  IVIT_LAUNCH_CHECK();
+  return 0;
+}
+
+extern "C" int ivit_adamw_chunked_ema(long n_tensors, void* const* params, void* const* grads, void* const* exp_avg,
+                                      void* const* exp_avg_sq, void* const* shadows, const long* sizes,
+                                      const int* chunks, long n_chunks, float lr, double beta1, double beta2,
+                                      float eps, float weight_decay, float bc1, float bc2_sqrt, const float* finite,
+                                      const float* steps_in, float* steps_out, const float* grad_scale,
+                                      void* const* emas, double ema_decay, int ema_warmup, void* stream) {
+  if (emas == nullptr)
+    return ivit_adamw_chunked_scaled(n_tensors, params, grads, exp_avg, exp_avg_sq, shadows, sizes, chunks, n_chunks,
+                                     lr, beta1, beta2, eps, weight_decay, bc1, bc2_sqrt, finite, steps_in, steps_out,
+                                     grad_scale, stream);
+  IVIT_CHECK_ARG(ema_decay >= 0.0 && ema_decay < 1.0, "ivit_adamw_chunked_ema: ema_decay must be in [0, 1) (got %g)",
+                 ema_decay);  // NaN fails too
+  IVIT_CHECK_ARG(!ema_warmup || steps_in != nullptr,
+                 "ivit_adamw_chunked_ema: ema_warmup needs the device step counts (without steps_in the host "
+                 "passes the step's decay as ema_decay)");
+  IVIT_CHECK_ARG(((uintptr_t)emas & 7) == 0, "ivit_adamw_chunked_ema: misaligned ema table");
+  if (n_tensors <= 0 || n_chunks <= 0) return 0;
+  IVIT_CHECK_ARG(chunks != nullptr && n_chunks < (1L << 31), "ivit_adamw_chunked_ema: bad chunk table");
+  IVIT_CHECK_ARG((steps_in == nullptr) == (steps_out == nullptr), "ivit_adamw_chunked_ema: steps_in / steps_out pair");
+  IVIT_CHECK_ARG(steps_in == nullptr || steps_in != steps_out, "ivit_adamw_chunked_ema: steps_out aliases steps_in");
+  IVIT_CHECK_ARG(((uintptr_t)chunks & 7) == 0, "ivit_adamw_chunked_ema: misaligned chunk table");
+  const dim3 grid((unsigned)n_chunks), block(256);
+  if (grad_scale != nullptr)
+    hipLaunchKernelGGL((adamw_chunk_kernel<true, true>), grid, block, 0, ivit_stream(stream), params, grads, exp_avg,
+                       exp_avg_sq, sizes, (const int2*)chunks, lr, (float)beta2, eps, weight_decay, bc1, bc2_sqrt,
+                       shadows, finite, steps_in, steps_out, beta1, beta2, (float)(1.0 - beta1), (float)(1.0 - beta2),
+                       grad_scale, emas, ema_decay, ema_warmup);
+  else
+    hipLaunchKernelGGL((adamw_chunk_kernel<false, true>), grid, block, 0, ivit_stream(stream), params, grads, exp_avg,
+                       exp_avg_sq, sizes, (const int2*)chunks, lr, (float)beta2, eps, weight_decay, bc1, bc2_sqrt,
+                       shadows, finite, steps_in, steps_out, beta1, beta2, (float)(1.0 - beta1), (float)(1.0 - beta2),
+                       (const float*)nullptr, emas, ema_decay, ema_warmup);
+  IVIT_LAUNCH_CHECK();
+  return 0;
+}
+
+extern "C" int ivit_swap_chunked(long n_tensors, void* const* a, void* const* b, const long* sizes, const int* chunks,
+                                 long n_chunks, void* const* shadows, void* stream) {
+  if (n_tensors <= 0 || n_chunks <= 0) return 0;
+  IVIT_CHECK_ARG(a != nullptr && b != nullptr && sizes != nullptr, "ivit_swap_chunked: null tensor tables");
+  IVIT_CHECK_ARG(chunks != nullptr && n_chunks < (1L << 31), "ivit_swap_chunked: bad chunk table");
+  IVIT_CHECK_ARG(((uintptr_t)chunks & 7) == 0, "ivit_swap_chunked: misaligned chunk table");
+  hipLaunchKernelGGL(swap_chunk_kernel, dim3((unsigned)n_chunks), dim3(256), 0, ivit_stream(stream), a, b, sizes,
+                     (const int2*)chunks, shadows);
   IVIT_LAUNCH_CHECK();
   return 0;
 }

@@ -26,6 +26,8 @@ were missed with and without a detection nearby, the translation / scale / orien
 true positives and the mAP each error type costs, and writes the same numbers to PATH as JSON
 (metrics.error_analysis, ivit_det_errors: all samples in one launch; ``--rotated`` picks the IoU).
 Without the flag the output is unchanged.
+``--ema`` evaluates the averaged weights a ``train_vit.py --ema-decay`` run saved ('ema_state_dict')
+instead of the last step's; a checkpoint without them is an error, not a fallback.
 """
 from __future__ import annotations
 
@@ -106,6 +108,8 @@ def parse_args(argv=None):
                     help="best IoU below which a detection is background, not a localisation error")
     ap.add_argument("--error-range-edges", type=str, default="20,40,60",
                     help="comma list of range-bin edges in metres from the ego vehicle (ascending, at most 7)")
+    ap.add_argument("--ema", action="store_true",
+                    help="load the checkpoint's 'ema_state_dict' (train_vit.py --ema-decay) instead of 'model_state_dict'")
     return ap.parse_args(argv)
 
 
@@ -219,7 +223,14 @@ def main_eval_vit(argv=None, variant="vit"):
         from model_cnn import IntentNetCNN
         model = IntentNetCNN(backbone_cfg=dict(cfg)).to(device)
         img_size = (H, W)
-    if ckpt is not None:
+    if args.ema:
+        if ckpt is None or 'ema_state_dict' not in ckpt:
+            print(f"ERROR: --ema: no 'ema_state_dict' in {args.checkpoint} (train with --ema-decay to save one).")
+            return 1
+        print(f"Evaluating the EMA weights ('ema_state_dict', decay {ckpt.get('ema_decay')}, "
+              f"warmup {ckpt.get('ema_warmup')})")
+        model.load_state_dict(ckpt['ema_state_dict'])
+    elif ckpt is not None:
         model.load_state_dict(ckpt['model_state_dict'])
     model.set_compute_dtype(torch.bfloat16 if args.dtype == "bf16" else torch.float32)
     model.eval()

@@ -3,6 +3,7 @@ betas (0.9, 0.999), eps 1e-8, decoupled weight decay) — one HIP launch per par
 over device pointer tables instead of torch's per-tensor foreach kernels."""
 from __future__ import annotations
 
+import contextlib
 import math
 
 import torch
@@ -86,6 +87,46 @@ class _Tables:
         lib.ivit_grad_scale(len(grads), ptr(self._table(grads, dev)), ptr(self._table_sizes(grads, dev)),
                             ptr(chunks) if nch else None, nch, ptr(coef), stream())
 
+    def _followers(self, ps):
+        """What follows the f32 weights ``ps`` and is rewritten when a launch changes them behind the
+        version counter: (bf16 shadow pointer per tensor, 0 = none; ivit_weight_pack_multi jobs of the
+        live row-panel packs; the largest pack in elements)."""
+        shadows, jobs, big = [], [], 0
+        for p in ps:
+            sh = ops.shadow_of(p)
+            shadows.append(sh.data_ptr() if sh is not None else 0)
+            pk, pkt = ops.packs_of(p)
+            rows, cols = p.shape[0], p.numel() // p.shape[0]
+            for pack, tr in ((pk, 0), (pkt, 1)):
+                if pack is not None:
+                    jobs.append((p.data_ptr(), pack.data_ptr(), rows, cols, tr))
+                    big = max(big, rows * cols)
+        return shadows, jobs, big
+
+    def _table_ptrs(self, ptrs, device):
+        key = ("ptrs",) + tuple(ptrs)
+        tab = self._tables.get(key)
+        if tab is None:
+            tab = torch.tensor(ptrs, dtype=torch.int64).pin_memory().to(device, non_blocking=True)
+            if len(self._tables) > 64:
+                self._tables.clear()
+            self._tables[key] = tab
+        return tab
+
+    def _pack_jobs(self, jobs, device):
+        """Device table of ivit_weight_pack_multi records (w, wpack, rows, cols, transposed), 40 B each."""
+        key = ("packs",) + tuple(jobs)
+        tab = self._tables.get(key)
+        if tab is None:
+            rec = []
+            for w, wp, rows, cols, tr in jobs:
+                rec += [w, wp, rows, cols, tr]
+            tab = torch.tensor(rec, dtype=torch.int64).pin_memory().to(device, non_blocking=True)
+            if len(self._tables) > 64:
+                self._tables.clear()
+            self._tables[key] = tab
+        return tab
+
 
 class GradNorm:
     """The device record of one ivit_grad_norm call: ``norm`` (the global L2 norm before clipping),
@@ -117,6 +158,21 @@ class FusedAdamW(torch.optim.Optimizer, _Tables):
         (``state['step']`` is a 0-d f32 device tensor, as torch's capturable AdamW keeps it) and a
         skipped update does not advance them, so the bias correction of every later step is the one
         torch.optim.AdamW applies when the reference's disconnected zero loss left no gradient."""
+        return self._step(closure, finite, grad_scale, None)
+
+    @torch.no_grad()
+    def step_ema(self, ema, closure=None, finite=None, grad_scale=None):
+        """``step`` that also moves ``ema`` (a ModelEMA; None = ``step``) in the same launch: every
+        updated parameter that ``ema`` tracks has its average moved towards the new weight,
+        e += (1 - d) * (p_new - e) with d = ``ema.decay_at(n)`` at the parameter's step count n after
+        this update. A parameter without a gradient, one ``ema`` does not track and an update that
+        ``finite`` = 0 skips all leave the average as it is. Weights, moments, counts and shadows
+        are the bits of ``step``."""
+        return self._step(closure, finite, grad_scale, ema)
+
+    def _step(self, closure, finite, grad_scale, ema):
+        if ema is not None and ema._swapped:
+            raise RuntimeError("FusedAdamW: the ModelEMA is swapped into the model (leave swapped() first)")
         loss = None
         if closure is not None:
             with torch.enable_grad():
@@ -138,10 +194,11 @@ class FusedAdamW(torch.optim.Optimizer, _Tables):
                     by_step.setdefault(st["step"], []).append(p)
                 for step, ps in by_step.items():
                     b1, b2 = group["betas"]
-                    self._launch(group, ps, 1.0 - b1 ** step, math.sqrt(1.0 - b2 ** step), None, None, None, grad_scale)
+                    self._launch(group, ps, 1.0 - b1 ** step, math.sqrt(1.0 - b2 ** step), None, None, None, grad_scale,
+                                 ema, step)
             else:
                 sin, sout = self._device_steps(live)
-                self._launch(group, live, 1.0, 1.0, finite, sin, sout, grad_scale)
+                self._launch(group, live, 1.0, 1.0, finite, sin, sout, grad_scale, ema)
                 for i, p in enumerate(live):
                     self.state[p]["step"] = sout[i]  # 0-d view; the other buffer is next step's output
         return loss
@@ -175,11 +232,14 @@ class FusedAdamW(torch.optim.Optimizer, _Tables):
         self._tables[key] = bufs
         return bufs
 
-    def _launch(self, group, ps, bc1, bc2s, finite, sin, sout, grad_scale=None):
+    def _launch(self, group, ps, bc1, bc2s, finite, sin, sout, grad_scale=None, ema=None, host_step=None):
         """The update of ``ps`` through the chunked streaming kernel (live bf16 compute copies,
         ops.cast_weight, rewritten in it), then every live row-panel weight pack (ops.packed_weight /
         packed_weight_t) rebuilt from the updated f32 weights in ONE launch: the pointer-table update
-        moves no version counter, so without it the packs would stay at the old weights."""
+        moves no version counter, so without it the packs would stay at the old weights.
+        ``ema`` (ModelEMA): its table goes to ivit_adamw_chunked_ema; with device counts the launch
+        forms the decay from steps_in, with host counts (``host_step``: the count after this update)
+        the host does and passes it with the warmup off."""
         b1, b2 = group["betas"]
         dev = ps[0].device
         st = [self.state[p] for p in ps]
@@ -188,21 +248,16 @@ class FusedAdamW(torch.optim.Optimizer, _Tables):
         tm = self._table([s["exp_avg"] for s in st], dev)
         tv = self._table([s["exp_avg_sq"] for s in st], dev)
         sizes = self._table_sizes(ps, dev)
-        shadows, jobs, big = [], [], 0
-        for p in ps:
-            sh = ops.shadow_of(p)
-            shadows.append(sh.data_ptr() if sh is not None else 0)
-            pk, pkt = ops.packs_of(p)
-            rows, cols = p.shape[0], p.numel() // p.shape[0]
-            for pack, tr in ((pk, 0), (pkt, 1)):
-                if pack is not None:
-                    jobs.append((p.data_ptr(), pack.data_ptr(), rows, cols, tr))
-                    big = max(big, rows * cols)
+        shadows, jobs, big = self._followers(ps)
         chunks, nch = self._table_chunks(ps, dev)
         args = (len(ps), ptr(tp), ptr(tg), ptr(tm), ptr(tv), ptr(self._table_ptrs(shadows, dev)), ptr(sizes),
                 ptr(chunks), nch, group["lr"], b1, b2, group["eps"], group["weight_decay"], bc1, bc2s, ptr(finite),
                 ptr(sin), ptr(sout))
-        if grad_scale is None:
+        if ema is not None:
+            te = self._table_ptrs(ema._ptrs(ps), dev)
+            decay, warm = (ema.decay, int(ema.warmup)) if sin is not None else (ema.decay_at(host_step), 0)
+            lib.ivit_adamw_chunked_ema(*args, ptr(grad_scale), ptr(te), decay, warm, stream())
+        elif grad_scale is None:
             lib.ivit_adamw_chunked(*args, stream())
         else:
             lib.ivit_adamw_chunked_scaled(*args, ptr(grad_scale), stream())
@@ -224,29 +279,106 @@ class FusedAdamW(torch.optim.Optimizer, _Tables):
                 self.state[p].update(step=0, exp_avg=flat[0, o:o + k].view_as(p), exp_avg_sq=flat[1, o:o + k].view_as(p))
                 o += k
 
-    def _table_ptrs(self, ptrs, device):
-        key = ("ptrs",) + tuple(ptrs)
-        tab = self._tables.get(key)
-        if tab is None:
-            tab = torch.tensor(ptrs, dtype=torch.int64).pin_memory().to(device, non_blocking=True)
-            if len(self._tables) > 64:
-                self._tables.clear()
-            self._tables[key] = tab
-        return tab
 
-    def _pack_jobs(self, jobs, device):
-        """Device table of ivit_weight_pack_multi records (w, wpack, rows, cols, transposed), 40 B each."""
-        key = ("packs",) + tuple(jobs)
-        tab = self._tables.get(key)
-        if tab is None:
-            rec = []
-            for w, wp, rows, cols, tr in jobs:
-                rec += [w, wp, rows, cols, tr]
-            tab = torch.tensor(rec, dtype=torch.int64).pin_memory().to(device, non_blocking=True)
-            if len(self._tables) > 64:
-                self._tables.clear()
-            self._tables[key] = tab
-        return tab
+class ModelEMA(_Tables):
+    """Exponential moving average of a model's parameters, kept by the optimiser's own launch
+    (FusedAdamW.step_ema / Trainer(ema=...)): e += (1 - d) (p - e) after every update, with
+    d = decay, or under ``warmup`` min(decay, (1 + n) / (10 + n)) at the parameter's step count n
+    (the usual ramp: a young average follows the weights closely). One flat f32 device buffer holds
+    every average, each starting at a multiple of 4 elements (16 bytes), initialised to the weights.
+    Buffers (BatchNorm statistics) are not averaged: ``state_dict`` takes them live from the model."""
+
+    def __init__(self, model_or_params, decay=0.9998, warmup=True):
+        super().__init__()
+        decay = float(decay)
+        if not 0.0 <= decay < 1.0:  # NaN fails too
+            raise ValueError(f"ModelEMA: decay must be in [0, 1) (got {decay})")
+        self.decay, self.warmup = decay, bool(warmup)
+        ps = model_or_params.parameters() if isinstance(model_or_params, torch.nn.Module) else model_or_params
+        self.params = [p for p in ps]
+        if not self.params:
+            raise ValueError("ModelEMA: no parameters")
+        dev = self.params[0].device
+        offs, n = [], 0
+        for p in self.params:
+            if not p.is_cuda:
+                raise RuntimeError("ivit ops take device tensors (no CPU fallback)")
+            if p.dtype != torch.float32 or not p.is_contiguous() or p.device != dev:
+                raise TypeError("ModelEMA: contiguous f32 parameters on one device required")
+            offs.append(n)
+            n += (p.numel() + 3) // 4 * 4
+        self.flat = torch.zeros(n, dtype=torch.float32, device=dev)
+        self._views = {id(p): self.flat[o:o + p.numel()].view_as(p) for p, o in zip(self.params, offs)}
+        with torch.no_grad():
+            torch._foreach_copy_([self._views[id(p)] for p in self.params], [p.detach() for p in self.params])
+        self._swapped = False
+
+    def decay_at(self, n):
+        """The decay of the update that brings a parameter to step count n (f64, as the launch forms it)."""
+        n = float(n)
+        return min(self.decay, (1.0 + n) / (10.0 + n)) if self.warmup else self.decay
+
+    def ema_of(self, p):
+        """The average of parameter p: a view of the flat buffer, shaped like p."""
+        return self._views[id(p)]
+
+    def _ptrs(self, ps):
+        """Average pointer per parameter of ``ps`` for the launch's table (0 = not tracked)."""
+        return [v.data_ptr() if v is not None else 0 for v in (self._views.get(id(p)) for p in ps)]
+
+    def _named(self, model):
+        return [(k, p) for k, p in model.named_parameters() if id(p) in self._views]
+
+    def state_dict(self, model):
+        """``model.state_dict()`` with every tracked parameter replaced by its average (a detached
+        view, as the model's own entries are); buffers are the model's, live."""
+        sd = model.state_dict()
+        for k, p in self._named(model):
+            if k not in sd:
+                raise KeyError(f"ModelEMA.state_dict: parameter {k} is not in the model's state dict")
+            sd[k] = self._views[id(p)].detach()
+        return sd
+
+    @torch.no_grad()
+    def load_state_dict(self, sd, model):
+        """The averages from ``sd`` (what ``state_dict`` returned; buffers are not read)."""
+        for k, p in self._named(model):
+            v = sd[k]
+            if tuple(v.shape) != tuple(p.shape):
+                raise ValueError(f"ModelEMA.load_state_dict: {k} has shape {tuple(v.shape)}, expected {tuple(p.shape)}")
+            self._views[id(p)].copy_(v)
+
+    def _swap(self, ps):
+        dev = ps[0].device
+        shadows, jobs, big = self._followers(ps)
+        chunks, nch = self._table_chunks(ps, dev)
+        lib.ivit_swap_chunked(len(ps), ptr(self._table(ps, dev)), ptr(self._table_ptrs(self._ptrs(ps), dev)),
+                              ptr(self._table_sizes(ps, dev)), ptr(chunks), nch, ptr(self._table_ptrs(shadows, dev)),
+                              stream())
+        if jobs:
+            lib.ivit_weight_pack_multi(len(jobs), ptr(self._pack_jobs(jobs, dev)), big, stream())
+
+    @contextlib.contextmanager
+    def swapped(self, model):
+        """Inside the block the model's tracked parameters hold the averages and this buffer holds the
+        live weights (ivit_swap_chunked, in place); the live bf16 shadows and row-panel packs are
+        rewritten from the new weights as FusedAdamW's launch rewrites them, so the forward inside
+        is the averaged model's. Swapped back on exit, also when the block raises. Not re-entrant,
+        and no optimiser step belongs inside."""
+        if self._swapped:
+            raise RuntimeError("ModelEMA.swapped: already swapped (nested use)")
+        ps = [p for _, p in self._named(model)]
+        if not ps:
+            raise ValueError("ModelEMA.swapped: the model has none of the tracked parameters")
+        with torch.no_grad():
+            self._swap(ps)
+        self._swapped = True
+        try:
+            yield self
+        finally:
+            with torch.no_grad():
+                self._swap(ps)
+            self._swapped = False
 
 
 _clip_tables = _Tables()

@@ -18,6 +18,10 @@ same per-batch NaN skips and the same checkpoint dict ({'epoch', 'model_state_di
   the kernels in bf16 with f32 master weights, ``fp32`` is the parity setting;
 * ``--clip-grad-norm X`` bounds the global gradient norm (trainer.Trainer ``max_grad_norm``); the
   epoch line then reports the mean and max norm and the clipped / skipped steps (one host read);
+* ``--ema-decay D`` keeps an exponential moving average of the weights in the optimiser's launch
+  (optim.ModelEMA, trainer.Trainer ``ema``; ``--ema-no-warmup`` drops the (1 + n) / (10 + n) ramp); the
+  checkpoint then also holds 'ema_state_dict' (the model's state dict with the averaged parameters),
+  'ema_decay' and 'ema_warmup', which ``eval_vit.py --ema`` evaluates. Off by default;
 * the reference's import-time defects (train_vit.py:34-35 undefined LIDAR_TOTAL_CHANNELS /
   MAP_CHANNELS, :131 ``verbose``) are fixed without changing any value.
 """
@@ -34,7 +38,7 @@ from constants import (ANCHOR_CONFIGS_PAPER, DOMINANT_CLASSES_FOR_DOWNSAMPLING, 
 from ddp import all_reduce_sum, any_rank, init_distributed
 from loss import DetectionIntentionLoss
 from model_vit import BasicBlock, IntentNetViT
-from optim import FusedAdamW
+from optim import FusedAdamW, ModelEMA
 from synthetic import SyntheticBEVLoader
 from trainer import Trainer
 from utils import generate_anchors
@@ -107,6 +111,11 @@ def parse_args(argv=None):
     ap.add_argument("--clip-grad-norm", type=float, default=GRAD_CLIP_NORM, metavar="X",
                     help="clip the global gradient L2 norm to X on the device (no host sync); a non-finite "
                          "gradient norm skips the update")
+    ap.add_argument("--ema-decay", type=float, default=None, metavar="D",
+                    help="keep an exponential moving average of the weights with decay D in [0, 1) (updated in the "
+                         "optimiser's launch) and save it as 'ema_state_dict'")
+    ap.add_argument("--ema-no-warmup", action="store_true",
+                    help="with --ema-decay: use D from the first step, without the min(D, (1 + n) / (10 + n)) ramp")
     return ap.parse_args(argv)
 
 
@@ -191,8 +200,12 @@ def main(argv=None, variant="vit"):
     scheduler = torch.optim.lr_scheduler.ReduceLROnPlateau(optimizer, mode='min', factor=0.1, patience=3)
     anchors = generate_anchors(H, W, stride, ANCHOR_CONFIGS_PAPER, device=device)
     log(f"Anchors generated (stride {stride}), shape: {tuple(anchors.shape)}")
+    ema = None
+    if args.ema_decay is not None:
+        ema = ModelEMA(model, decay=args.ema_decay, warmup=not args.ema_no_warmup)
+        log(f"Weight EMA: decay {ema.decay:g}, warmup {ema.warmup}")
     trainer = Trainer(model, loss_fn, optimizer, anchors, world=world, bucket_mb=args.bucket_mb, check_nan=True,
-                      max_grad_norm=args.clip_grad_norm)
+                      max_grad_norm=args.clip_grad_norm, ema=ema)
 
     log(f"\n--- Starting {tag} Training ---")
     for epoch in range(args.epochs):
@@ -230,8 +243,11 @@ def main(argv=None, variant="vit"):
         save_dir = Path(args.save_dir)
         save_dir.mkdir(parents=True, exist_ok=True)
         path = save_dir / f"{variant}_model.pth"
-        torch.save({'epoch': args.epochs, 'model_state_dict': model.state_dict(),
-                    'optimizer_state_dict': optimizer.state_dict(), 'backbone_cfg': cfg}, path)
+        ckpt = {'epoch': args.epochs, 'model_state_dict': model.state_dict(),
+                'optimizer_state_dict': optimizer.state_dict(), 'backbone_cfg': cfg}
+        if ema is not None:
+            ckpt.update(ema_state_dict=ema.state_dict(model), ema_decay=ema.decay, ema_warmup=ema.warmup)
+        torch.save(ckpt, path)
         log(f"Saved final TRAINED {tag} model to {path}")
     if world > 1:
         torch.distributed.destroy_process_group()

@@ -28,6 +28,12 @@ update launch multiplies each gradient by the clip coefficient as it loads it an
 non-finite loss does (weights, moments and device step counts unchanged). The loss dict gains
 ``grad_norm`` (the norm before clipping, a 0-d device tensor); ``clipped`` / ``nonfinite_grad`` /
 ``grad_stats()`` read the device accumulator on demand.
+
+``ema`` (optim.ModelEMA; None = off, exactly the step above): every optimiser call becomes
+``FusedAdamW.step_ema``, whose launch moves the average towards the weight it has just written. A
+batch the host checks skip never reaches the optimiser and a launch that reads finite = 0 writes
+nothing, so neither moves the average. Under DDP nothing is communicated for it: the parameters are
+bit-identical on every rank after the update, and so is the average.
 """
 from __future__ import annotations
 
@@ -35,12 +41,19 @@ import torch
 
 from ddp import GradBuckets, any_rank, broadcast_state, grad_order, min_on_device
 from loss import device_guard
-from optim import STATS_FIELDS, FusedAdamW
+from optim import STATS_FIELDS, FusedAdamW, ModelEMA
 
 
 class Trainer:
     def __init__(self, model, loss_fn, optimizer, anchors, world: int = 1, bucket_mb: float = 64.0,
-                 check_nan: bool = True, force_buckets: bool = False, max_grad_norm: float | None = None):
+                 check_nan: bool = True, force_buckets: bool = False, max_grad_norm: float | None = None,
+                 ema: ModelEMA | None = None):
+        if ema is not None:
+            if not isinstance(ema, ModelEMA):
+                raise TypeError("Trainer: ema is an optim.ModelEMA or None")
+            if not isinstance(optimizer, FusedAdamW):
+                raise TypeError("Trainer: ema needs FusedAdamW (the average is part of its launch)")
+        self.ema = ema
         if max_grad_norm is not None:
             if not float(max_grad_norm) > 0.0:
                 raise ValueError(f"Trainer: max_grad_norm must be > 0 or None (got {max_grad_norm})")
@@ -93,6 +106,11 @@ class Trainer:
             return bool(torch.isfinite(d["loss"]).all())
         return bool(fin) and not bool(torch.isnan(d["loss"]))
 
+    def _opt_step(self, **kw):
+        if self.ema is None:
+            return self.optimizer.step(**kw)
+        return self.optimizer.step_ema(self.ema, **kw)
+
     def step(self, batch: dict):
         """Returns the loss dict, or None when the batch was skipped (NaN in the outputs)."""
         lidar, mp, gts = batch["lidar_bev"], batch["map_bev"], batch["gt_list"]
@@ -120,14 +138,14 @@ class Trainer:
             if self._grad_stats is None:
                 self._grad_stats = torch.zeros(len(STATS_FIELDS), dtype=torch.float64, device=dev)
             gn = self.optimizer.grad_norm(self.max_grad_norm, finite=fin, stats=self._grad_stats)
-            self.optimizer.step(finite=gn.finite, grad_scale=gn.coef)
+            self._opt_step(finite=gn.finite, grad_scale=gn.coef)
             d["grad_norm"] = gn.norm
         elif not self.check_nan and fin is not None and isinstance(self.optimizer, FusedAdamW):
             # no host sync: the update launch itself reads the loss's finite flag and does nothing
             # on 0 (weights and moments unchanged, as with the reference's disconnected zero loss)
             if self.buckets is not None and self.world > 1:
                 fin = min_on_device(fin)  # every rank skips together (replicas stay identical)
-            self.optimizer.step(finite=fin)
+            self._opt_step(finite=fin)
         else:
-            self.optimizer.step()
+            self._opt_step()
         return d
