@@ -174,7 +174,8 @@ int ivit_conv_wgrad(int dtype, const void* dY, long lddy, const void* X, long B,
                     long Cout, long ks, float* dWp, float* dbias, int accumulate, void* work, long work_bytes,
                     void* stream);
 /* Data gradient on the transposed, tap-flipped pack of ivit_pack_conv_weight_t (bf16; the 288 x 256
- * panel kernel: Cout % 64 == 0, Cin % 8 == 0, B*H*W >= 288); same sums as ivit_conv_dgrad. */
+ * panel kernel: Cout % 64 == 0, Cin >= 128, Cin % 8 == 0, lddy % 8 == 0, B*H*W >= 288, ks in {1, 3, 5};
+ * IVIT_ERR_ARG otherwise); same sums as ivit_conv_dgrad. */
 int ivit_conv_dgrad_t(int dtype, const void* dY, long lddy, long B, long H, long W, long Cout, const void* WpT,
                       long Cin, long ks, void* dX, int dx_dtype, void* stream);
 /* Convolution + the following BatchNorm2d's training-mode batch statistics in one pass (BasicBlock
@@ -182,7 +183,8 @@ int ivit_conv_dgrad_t(int dtype, const void* dY, long lddy, long B, long H, long
  * invstd (biased variance, eps) of Y's channels, running mean / var updated with momentum (unbiased
  * variance) as ivit_bn_stats. bf16 panel shapes fold the statistics into the convolution's epilogue
  * (per-tile sums and centred squares, merged across tiles in a fixed order); other shapes run
- * ivit_conv_fwd + ivit_bn_stats. */
+ * ivit_conv_fwd + ivit_bn_stats. Either way the statistics are those of Y as stored (of the rounded
+ * values for a bf16 Y). */
 long ivit_conv_bn_fwd_workspace(long B, long H, long W, long Cout);
 int ivit_conv_bn_fwd(int dtype, const void* X, long B, long H, long W, long Cin, const void* Wp, long Cout, long ks,
                      void* Y, long ldy, int y_dtype, float* mean, float* invstd, float* run_mean, float* run_var,
@@ -571,8 +573,10 @@ int ivit_map_raster(const int* seg, long n_seg, const long* seg_base, const long
  * [B*Ho*Wo, ldc] row (b, oy, ox), column (ky*k + kx)*C + c = X[b, oy*s - pad + ky,
  * ox*s - pad + kx, c] (0 outside the map and in columns k*k*C .. ldc-1), i.e. the
  * [Cout][k][k][Cin] packed weight viewed [Cout, k*k*C] is the GEMM operand; Ho, Wo follow
- * nn.Conv2d (floor((H + 2 pad - k) / s) + 1). col2im (C <= 512) is the adjoint as a gather: dX (f32, NHWC)
- * = sum over (ky, kx) ascending of the dcols entries whose window covers the pixel.       */
+ * nn.Conv2d (floor((H + 2 pad - k) / s) + 1; H + 2 pad >= k and W + 2 pad >= k). Dtype pairs
+ * f32 -> f32, f32 -> bf16 (round to nearest even), bf16 -> bf16. col2im (C <= 512) is the adjoint
+ * as a gather: dX (f32, NHWC) = sum over (ky, kx) ascending of the dcols entries whose window
+ * covers the pixel (0 where none does); columns k*k*C .. ldc-1 of dcols are not read.       */
 int ivit_im2col(int x_dtype, const void* X, long B, long H, long W, long C, long k, long stride, long pad, long Ho,
                 long Wo, void* cols, long ldc, int cols_dtype, void* stream);
 int ivit_col2im(const float* dcols, long ldc, long B, long H, long W, long C, long k, long stride, long pad, long Ho,

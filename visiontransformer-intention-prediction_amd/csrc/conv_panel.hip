@@ -201,6 +201,18 @@ __global__ __launch_bounds__(512, 1) void conv_panel_kernel(CpArgs p) {
     // Channel c = 64 wn + 16 j + 4 (lane >> 4) + e of the tile sits in the 16 lanes of one lane
     // group and the 9 blocks mb of both row waves wm.
     float* red = (float*)smem;  // [2 passes][2 wm][256]
+    if constexpr (sizeof(O) == 2) {
+      // a bf16 Y: the statistics are those of the values stored below (what the BatchNorm reads and
+      // what the fallback's ivit_bn_stats sees), so round the accumulators as the store does
+#pragma unroll
+      for (int j = 0; j < CP_NB; ++j)
+#pragma unroll
+        for (int mb = 0; mb < CP_MB; ++mb) {
+          const unsigned u0 = pk_bf16(acc[mb][j][0], acc[mb][j][1]), u1 = pk_bf16(acc[mb][j][2], acc[mb][j][3]);
+          acc[mb][j] = f32x4{__builtin_bit_cast(float, u0 << 16), __builtin_bit_cast(float, u0 & 0xffff0000u),
+                             __builtin_bit_cast(float, u1 << 16), __builtin_bit_cast(float, u1 & 0xffff0000u)};
+        }
+    }
     __builtin_amdgcn_s_barrier();  // every wave is past its last fragment read of the stages
     const int nv = min(CP_BM, p.M - m0);
     float sm[CP_NB][4];

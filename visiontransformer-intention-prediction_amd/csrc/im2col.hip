@@ -85,6 +85,7 @@ __global__ __launch_bounds__(256) void col2im_kernel(const float* __restrict__ d
 extern "C" int ivit_im2col(int x_dtype, const void* X, long B, long H, long W, long C, long k, long stride, long pad,
                            long Ho, long Wo, void* cols, long ldc, int cols_dtype, void* stream) {
   IVIT_CHECK_ARG(B > 0 && H > 0 && W > 0 && C > 0 && k > 0 && stride > 0 && pad >= 0, "ivit_im2col: bad shape");
+  IVIT_CHECK_ARG(H + 2 * pad >= k && W + 2 * pad >= k, "ivit_im2col: the padded map is smaller than the kernel");
   IVIT_CHECK_ARG(Ho == (H + 2 * pad - k) / stride + 1 && Wo == (W + 2 * pad - k) / stride + 1 && Ho > 0 && Wo > 0,
                  "ivit_im2col: output size %ldx%ld does not match the conv geometry", Ho, Wo);
   IVIT_CHECK_ARG(ldc >= k * k * C, "ivit_im2col: ldc %ld < k*k*C", ldc);
@@ -108,6 +109,7 @@ extern "C" int ivit_im2col(int x_dtype, const void* X, long B, long H, long W, l
 extern "C" int ivit_col2im(const float* dcols, long ldc, long B, long H, long W, long C, long k, long stride,
                            long pad, long Ho, long Wo, float* dX, void* stream) {
   IVIT_CHECK_ARG(B > 0 && H > 0 && W > 0 && C > 0 && k > 0 && stride > 0 && pad >= 0, "ivit_col2im: bad shape");
+  IVIT_CHECK_ARG(H + 2 * pad >= k && W + 2 * pad >= k, "ivit_col2im: the padded map is smaller than the kernel");
   IVIT_CHECK_ARG(Ho == (H + 2 * pad - k) / stride + 1 && Wo == (W + 2 * pad - k) / stride + 1,
                  "ivit_col2im: output size does not match the conv geometry");
   IVIT_CHECK_ARG(ldc >= k * k * C, "ivit_col2im: ldc %ld < k*k*C", ldc);
