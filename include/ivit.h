@@ -162,6 +162,33 @@ int ivit_patch_tokens_bwd(const void* dtok, int dtok_dtype, long B, long Np, lon
 int ivit_bilinear_fwd(const float* X, long Z, long Hi, long Wi, float* Y, long Ho, long Wo, void* stream);
 int ivit_bilinear_bwd(const float* dY, long Z, long Hi, long Wi, long Ho, long Wo, float* dX, void* stream);
 
+/* ---- Loading pretrained / other-grid checkpoints (timm vision_transformer.checkpoint_filter_fn;
+ *      the reference's pretrained_lidar / pretrained_map, model_vit.py:64,71). Load-time only.
+ * ivit_pos_resample = timm resample_abs_pos_embed's F.interpolate(mode='bicubic', antialias=True,
+ * align_corners=False) of the patch part of pos_embed: src f32 [h, w, D] channels last (the
+ * [1, D, h, w] view of pos_embed[0, prefix:], no permute), dst f32 [oh, ow, D]. Separable, width
+ * pass then height pass; per axis, n_in -> n_out:
+ *   scale = n_in / n_out;  support = scale >= 1 ? 2 scale : 2;  inv = scale >= 1 ? 1 / scale : 1
+ *   output i:  c = scale (i + 0.5);  xmin = max(0, (int)(c - support + 0.5));
+ *              xmax = min((int)(c + support + 0.5), n_in)
+ *   w_j = k((j - c + 0.5) inv) for j in [xmin, xmax), divided by their sum;  out_i = sum_j w_j in_j
+ *   k(x) = ((a + 2)|x| - (a + 3)) x^2 + 1        for |x| < 1        (Keys cubic, a = -0.5)
+ *        = (((|x| - 5)|x| + 8)|x| - 4) a         for 1 <= |x| < 2;   0 beyond
+ * Up-sampling has 4 taps per axis, down-sampling by s about 4 s (any count). Weights, their
+ * normalisation and the sums are f64 (the width pass leaves an f64 [h, ow, D] intermediate in
+ * work), so the result is the f64 value rounded once to f32; equal sizes reproduce src exactly.
+ * A gather, no atomics: bitwise repeatable. work: 8-B aligned, >= ivit_pos_resample_workspace bytes
+ * (0 for sizes the op refuses). Refused before any device call: non-positive or > 2^30 sizes, null
+ * pointers, a workspace too small.                                                               */
+long ivit_pos_resample_workspace(long h, long w, long D, long oh, long ow);
+int ivit_pos_resample(const float* src, long h, long w, long D, float* dst, long oh, long ow, void* work,
+                      long work_bytes, void* stream);
+/* timm adapt_input_conv: conv weight f32 [O, I, kh, kw] -> [O, C, kh, kw].  C == I: copy;
+ * I == 3, C == 1: the sum over the input channels;  I == 3, other C: out[:, c] = in[:, c mod 3] *
+ * (float)(3.0 / C)  (timm's repeat(1, ceil(C / 3), 1, 1)[:, :C] * (3 / C));  any other I is refused
+ * (timm raises NotImplementedError), as are null pointers and non-positive sizes.                 */
+int ivit_adapt_input_conv(const float* w_in, long O, long I, long kh, long kw, float* w_out, long C, void* stream);
+
 /* ---- k x k stride-1 "same" convolution on NHWC maps (BasicBlock conv3x3/conv1x1,
  *      model_vit.py:12-17; DetectionHead/IntentionHead conv, heads.py:16,37; k = 5: model_cnn.py:7-9).
  *      Weights packed [Cout][k][k][Cin] (see ivit_pack_conv_weight).                           */

@@ -28,6 +28,10 @@ true positives and the mAP each error type costs, and writes the same numbers to
 Without the flag the output is unchanged.
 ``--ema`` evaluates the averaged weights a ``train_vit.py --ema-decay`` run saved ('ema_state_dict')
 instead of the last step's; a checkpoint without them is an error, not a fallback.
+``--regrid`` evaluates a checkpoint at ``--grid`` instead of the grid it was trained at: the model is
+built at ``--grid`` and the two streams' pos_embed are resampled onto it (bicubic, antialiased:
+model_vit.load_state_dict_regrid); everything else loads bit for bit. Without the flag the model has
+the checkpoint's ``img_size``, as before.
 """
 from __future__ import annotations
 
@@ -110,6 +114,9 @@ def parse_args(argv=None):
                     help="comma list of range-bin edges in metres from the ego vehicle (ascending, at most 7)")
     ap.add_argument("--ema", action="store_true",
                     help="load the checkpoint's 'ema_state_dict' (train_vit.py --ema-decay) instead of 'model_state_dict'")
+    ap.add_argument("--regrid", action="store_true",
+                    help="build the model at --grid instead of the checkpoint's img_size and resample the streams' "
+                         "pos_embed onto it (ViT only)")
     return ap.parse_args(argv)
 
 
@@ -189,6 +196,8 @@ def main_eval_vit(argv=None, variant="vit"):
     tag = "ViT" if variant == "vit" else "CNN"
     if args.attn_maps is not None and variant != "vit":
         raise SystemExit("--attn-maps: IntentNetCNN has no attention to map (use eval_vit.py)")
+    if args.regrid and variant != "vit":
+        raise SystemExit("--regrid: IntentNetCNN has no position embedding tied to a grid (use eval_vit.py)")
     if args.checkpoint is None:
         args.checkpoint = MODEL_SAVE_PATH_VIT if variant == "vit" else MODEL_SAVE_PATH_CNN
     if not torch.cuda.is_available():
@@ -217,6 +226,9 @@ def main_eval_vit(argv=None, variant="vit"):
         return 1
     if variant == "vit":
         cfg = default_cfg(dict(cfg), (H, W))
+        src_img_size = tuple(cfg['img_size'])
+        if args.regrid:
+            cfg['img_size'] = (H, W)
         model = IntentNetViT(backbone_cfg=cfg).to(device)
         img_size = tuple(cfg['img_size'])
     else:
@@ -229,9 +241,15 @@ def main_eval_vit(argv=None, variant="vit"):
             return 1
         print(f"Evaluating the EMA weights ('ema_state_dict', decay {ckpt.get('ema_decay')}, "
               f"warmup {ckpt.get('ema_warmup')})")
-        model.load_state_dict(ckpt['ema_state_dict'])
-    elif ckpt is not None:
-        model.load_state_dict(ckpt['model_state_dict'])
+        weights = ckpt['ema_state_dict']
+    else:
+        weights = ckpt['model_state_dict'] if ckpt is not None else None
+    if weights is not None and args.regrid:
+        done = model_vit.load_state_dict_regrid(model, weights, src_img_size)
+        for key, (old, new) in done.items():
+            print(f"--regrid: {key} {old[0]}x{old[1]} -> {new[0]}x{new[1]}")
+    elif weights is not None:
+        model.load_state_dict(weights)
     model.set_compute_dtype(torch.bfloat16 if args.dtype == "bf16" else torch.float32)
     model.eval()
 

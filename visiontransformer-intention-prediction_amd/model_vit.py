@@ -59,29 +59,32 @@ class TwoStreamViTBackbone(nn.Module):
                  pretrained_lidar=False, pretrained_map=False, img_size=(GRID_HEIGHT_PX, GRID_WIDTH_PX),
                  drop_path_rate_lidar=0.1, drop_path_rate_map=0.1, lidar_adapter_out_channels=192,
                  map_adapter_out_channels=192, fusion_block_planes=512, fusion_block_layers=2,
-                 fusion_block_kernel_size=3, fusion_block_stride=1, res_block_type=BasicBlock):
+                 fusion_block_kernel_size=3, fusion_block_stride=1, res_block_type=BasicBlock,
+                 pretrained_lidar_file=None, pretrained_map_file=None):
+        """The reference's arguments (model_vit.py:38-47). ``pretrained_lidar`` / ``pretrained_map``
+        load timm weights of the stream's architecture from a local file (vit.create_model:
+        $IVIT_PRETRAINED_DIR/<name>.safetensors|.pth|.bin); ``pretrained_lidar_file`` /
+        ``pretrained_map_file`` name the file directly and imply pretrained for that stream."""
         super().__init__()
         self.img_size = tuple(img_size)
         self.lidar_adapter_out_channels = lidar_adapter_out_channels
         self.map_adapter_out_channels = map_adapter_out_channels
-        self.vit_lidar = timm_like.create_model(vit_model_name_lidar, pretrained=pretrained_lidar,
+        over_l = {"file": pretrained_lidar_file} if pretrained_lidar_file is not None else None
+        over_m = {"file": pretrained_map_file} if pretrained_map_file is not None else None
+        self.vit_lidar = timm_like.create_model(vit_model_name_lidar, pretrained=bool(pretrained_lidar or over_l),
                                                 in_chans=lidar_input_channels, img_size=self.img_size,
-                                                drop_path_rate=drop_path_rate_lidar)
+                                                drop_path_rate=drop_path_rate_lidar, pretrained_cfg_overlay=over_l)
         self.vit_lidar.head = nn.Identity()
         self.lidar_embed_dim = self.vit_lidar.embed_dim
         self.lidar_num_prefix_tokens = self.vit_lidar.num_prefix_tokens
         self.lidar_grid_size = tuple(self.vit_lidar.patch_embed.grid_size)
-        self.vit_map = timm_like.create_model(vit_model_name_map, pretrained=pretrained_map,
+        self.vit_map = timm_like.create_model(vit_model_name_map, pretrained=bool(pretrained_map or over_m),
                                               in_chans=map_input_channels, img_size=self.img_size,
-                                              drop_path_rate=drop_path_rate_map)
+                                              drop_path_rate=drop_path_rate_map, pretrained_cfg_overlay=over_m)
         self.vit_map.head = nn.Identity()
         self.map_embed_dim = self.vit_map.embed_dim
         self.map_num_prefix_tokens = self.vit_map.num_prefix_tokens
-        self.map_grid_size = tuple(self.vit_map.patch_embed.grid_size)
-        if self.lidar_grid_size != self.map_grid_size:
-            # model_vit.py:76-77; forward re-grids the map features bilinearly (:139)
-            warnings.warn(f"LiDAR patch grid {self.lidar_grid_size} and Map patch grid {self.map_grid_size} differ.")
-        self.feature_map_grid_h, self.feature_map_grid_w = self.lidar_grid_size
+        self._read_grids()
         self.adapter_lidar = nn.Sequential(LayerNorm(self.lidar_embed_dim),
                                            Linear(self.lidar_embed_dim, lidar_adapter_out_channels), GELU())
         self.adapter_map = nn.Sequential(LayerNorm(self.map_embed_dim),
@@ -94,6 +97,23 @@ class TwoStreamViTBackbone(nn.Module):
                                                     kernel_size_for_block=fusion_block_kernel_size)
         self.final_feature_channels = fusion_block_planes * res_block_type.expansion
         self.fusion_layers = fusion_block_layers
+
+    def _read_grids(self):
+        """The attributes derived from the two streams' patch grids (model_vit.py:66-79)."""
+        self.lidar_grid_size = tuple(self.vit_lidar.patch_embed.grid_size)
+        self.map_grid_size = tuple(self.vit_map.patch_embed.grid_size)
+        if self.lidar_grid_size != self.map_grid_size:
+            # model_vit.py:76-77; forward re-grids the map features bilinearly (:139)
+            warnings.warn(f"LiDAR patch grid {self.lidar_grid_size} and Map patch grid {self.map_grid_size} differ.")
+        self.feature_map_grid_h, self.feature_map_grid_w = self.lidar_grid_size
+
+    def set_input_size(self, img_size):
+        """Both streams to another input size (vit.VisionTransformer.set_input_size: their pos_embed
+        Parameters are replaced by resampled ones) and the derived grid attributes with them."""
+        self.vit_lidar.set_input_size(img_size)
+        self.vit_map.set_input_size(img_size)
+        self.img_size = (int(img_size[0]), int(img_size[1]))
+        self._read_grids()
 
     def _get_patch_info(self, vit_model, stream_name=""):
         pe = vit_model.patch_embed
@@ -268,6 +288,34 @@ def _lookup(root, names):
     return [sd[n] for n in names]
 
 
+REGRID_KEYS = (("backbone.vit_lidar.pos_embed", "vit_lidar"), ("backbone.vit_map.pos_embed", "vit_map"))
+
+
+def load_state_dict_regrid(model, state_dict, src_img_size):
+    """``model.load_state_dict(state_dict)`` (strict) for a state dict saved at another BEV grid:
+    the two streams' pos_embed are first resampled from the grid ``src_img_size`` gives under each
+    stream's patch size onto the model's (vit.resample_abs_pos_embed); every other tensor loads bit
+    for bit. A model without ViT streams (IntentNetCNN has no position embedding) loads as it is.
+    Returns {key: (old grid, new grid)} of the resampled entries."""
+    sd = dict(state_dict)
+    done = {}
+    bb = getattr(model, "backbone", None)
+    for key, attr in REGRID_KEYS:
+        vit = getattr(bb, attr, None)
+        if vit is None or key not in sd:
+            continue
+        p = vit.patch_embed.patch_size[0]
+        old = (int(src_img_size[0]) // p, int(src_img_size[1]) // p)
+        new = tuple(vit.patch_embed.grid_size)
+        if old != new:
+            dev = timm_like._op_device(vit.pos_embed.device)
+            sd[key] = timm_like.resample_abs_pos_embed(sd[key].to(dev), new, old_size=old,
+                                                       num_prefix_tokens=vit.num_prefix_tokens)
+            done[key] = (old, new)
+    model.load_state_dict(sd, strict=True)
+    return done
+
+
 class IntentNetViT(nn.Module):
     def __init__(self, backbone_cfg: dict | None = None, head_cfg: dict | None = None):
         super().__init__()
@@ -304,6 +352,15 @@ class IntentNetViT(nn.Module):
         assert dtype in (torch.float32, torch.bfloat16)
         for m in self.modules():
             m.compute_dtype = dtype
+        return self
+
+    def set_input_size(self, img_size):
+        """Carry the model to another BEV grid: both ViT streams' pos_embed resampled (bicubic,
+        antialiased, as timm does when it loads a checkpoint at another size) and the backbone's
+        img_size / lidar_grid_size / map_grid_size / feature_map_grid_h/w updated. Everything else is
+        size-free. It replaces the two pos_embed Parameters, so it must run before an optimizer or a
+        ModelEMA is built on the model."""
+        self.backbone.set_input_size(img_size)
         return self
 
     def attention_maps(self, lidar_bev, map_bev, sample, centers_xy_m, blocks=(-1,), head_mean=True):

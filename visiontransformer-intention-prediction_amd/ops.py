@@ -327,6 +327,41 @@ class BilinearFn(torch.autograd.Function):
         return bilinear_bwd(dy.float(), ctx.in_size), None
 
 
+def pos_resample(src, size):
+    """F.interpolate(mode='bicubic', antialias=True, align_corners=False) of a channels-last f32
+    [h, w, D] field (the patch rows of a pos_embed) onto ``size`` = (oh, ow): f32 [oh, ow, D]
+    (ivit_pos_resample; timm resample_abs_pos_embed). Load-time, no autograd."""
+    if not src.is_cuda:
+        raise RuntimeError("ops.pos_resample takes a device tensor (no CPU fallback)")
+    if src.dim() != 3:
+        raise ValueError(f"ops.pos_resample: expected [h, w, D], got {tuple(src.shape)}")
+    oh, ow = (int(v) for v in size)
+    with torch.no_grad():
+        src = src.detach().float().contiguous()
+        h, w, D = src.shape
+        dst = torch.empty((oh, ow, D), dtype=torch.float32, device=src.device)
+        nb = lib.ivit_pos_resample_workspace(h, w, D, oh, ow)
+        work = workspace(nb, src.device)
+        lib.ivit_pos_resample(ptr(src), h, w, D, ptr(dst), oh, ow, ptr(work), work.numel(), stream())
+    return dst
+
+
+def adapt_input_conv(weight, in_chans):
+    """timm adapt_input_conv on the device: an f32 [O, I, kh, kw] conv weight for ``in_chans`` input
+    channels, [O, in_chans, kh, kw] (ivit_adapt_input_conv). Load-time, no autograd."""
+    if not weight.is_cuda:
+        raise RuntimeError("ops.adapt_input_conv takes a device tensor (no CPU fallback)")
+    if weight.dim() != 4:
+        raise ValueError(f"ops.adapt_input_conv: expected [O, I, kh, kw], got {tuple(weight.shape)}")
+    C = int(in_chans)
+    with torch.no_grad():
+        weight = weight.detach().float().contiguous()
+        O, I, kh, kw = weight.shape
+        out = torch.empty((O, max(C, 0), kh, kw), dtype=torch.float32, device=weight.device)
+        lib.ivit_adapt_input_conv(ptr(weight), O, I, kh, kw, ptr(out), C, stream())
+    return out
+
+
 def attn_fwd(qkv, B, N, H, cdt):
     D = H * 64
     out = torch.empty((B * N, D), dtype=qkv.dtype, device=qkv.device)

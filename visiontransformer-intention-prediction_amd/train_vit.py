@@ -22,6 +22,11 @@ same per-batch NaN skips and the same checkpoint dict ({'epoch', 'model_state_di
   (optim.ModelEMA, trainer.Trainer ``ema``; ``--ema-no-warmup`` drops the (1 + n) / (10 + n) ramp); the
   checkpoint then also holds 'ema_state_dict' (the model's state dict with the averaged parameters),
   'ema_decay' and 'ema_warmup', which ``eval_vit.py --ema`` evaluates. Off by default;
+* ``--pretrained-lidar PATH`` / ``--pretrained-map PATH`` initialise a stream's ViT from a timm checkpoint
+  (vit.VisionTransformer.load_pretrained: pos_embed resampled onto ``--grid``, the 3-channel patch weights
+  adapted to the stream's channels); the saved 'backbone_cfg' keeps ``pretrained_*: False``, so the
+  checkpoint stays self-contained. ``--init-from CKPT`` starts from the weights of one of this script's
+  checkpoints, trained at the same or another grid (model_vit.load_state_dict_regrid);
 * the reference's import-time defects (train_vit.py:34-35 undefined LIDAR_TOTAL_CHANNELS /
   MAP_CHANNELS, :131 ``verbose``) are fixed without changing any value.
 """
@@ -116,7 +121,43 @@ def parse_args(argv=None):
                          "optimiser's launch) and save it as 'ema_state_dict'")
     ap.add_argument("--ema-no-warmup", action="store_true",
                     help="with --ema-decay: use D from the first step, without the min(D, (1 + n) / (10 + n)) ramp")
+    ap.add_argument("--pretrained-lidar", type=str, default=None, metavar="PATH",
+                    help="timm weights (.pth / .bin / .safetensors) of the LiDAR stream's ViT: pos_embed resampled "
+                         "to --grid, the 3-channel patch weights adapted to the LiDAR channels (ViT only)")
+    ap.add_argument("--pretrained-map", type=str, default=None, metavar="PATH",
+                    help="the same for the map stream's ViT")
+    ap.add_argument("--init-from", type=str, default=None, metavar="CKPT",
+                    help="start from the 'model_state_dict' of one of this script's checkpoints, trained at the "
+                         "same or another --grid (pos_embed resampled); its optimizer state is not taken")
     return ap.parse_args(argv)
+
+
+def _grid_str(g):
+    return f"{g[0]}x{g[1]}"
+
+
+def load_initial_weights(model, args, variant, device, log):
+    """--init-from, then --pretrained-lidar / --pretrained-map, on the freshly built model (before the
+    optimizer, the EMA and the Trainer exist: a resampled pos_embed replaces nothing they hold). Every
+    rank reads the same files, so the replicas start identical. One log line per load."""
+    if args.init_from is not None:
+        from eval_vit import load_checkpoint
+        from model_vit import load_state_dict_regrid
+        ckpt = load_checkpoint(args.init_from, device)
+        src = tuple((ckpt.get('backbone_cfg') or {}).get('img_size', (0, 0)))
+        if variant == "vit" and src == (0, 0):
+            raise SystemExit(f"--init-from {args.init_from}: no backbone_cfg['img_size'] in the checkpoint")
+        done = load_state_dict_regrid(model, ckpt['model_state_dict'], src)
+        what = ", ".join(f"{k.split('.')[1]} pos_embed {_grid_str(o)} -> {_grid_str(n)}" for k, (o, n) in done.items())
+        log(f"Initialised from {args.init_from} (model_state_dict; {what or 'same grid, loaded as saved'})")
+    for name, path in (("vit_lidar", args.pretrained_lidar), ("vit_map", args.pretrained_map)):
+        if path is None:
+            continue
+        info = getattr(model.backbone, name).load_pretrained(path)
+        og, ch = info["old_grid"], info["in_chans"]
+        log(f"Pretrained {name} from {path}: pos_embed "
+            + (f"{_grid_str(og)} -> {_grid_str(info['new_grid'])}" if og else f"{_grid_str(info['new_grid'])} as saved")
+            + (f", patch weights {ch[0]} -> {ch[1]} channels" if ch else ", patch weights as saved"))
 
 
 def grad_clip_line(st, max_norm):
@@ -145,6 +186,9 @@ def main(argv=None, variant="vit"):
     tag = "ViT" if variant == "vit" else "CNN"
     if args.save_dir is None:
         args.save_dir = MODEL_SAVE_DIR_VIT if variant == "vit" else MODEL_SAVE_DIR_CNN
+    if variant != "vit" and (args.pretrained_lidar is not None or args.pretrained_map is not None):
+        raise SystemExit("--pretrained-lidar / --pretrained-map: IntentNetCNN has no ViT stream to load timm weights "
+                         "into (use train_vit.py; --init-from works for both)")
     rank, local, world, device = init_distributed()
     if device.type != "cuda":
         raise RuntimeError("train_vit.py runs on the MI355X kernels: no ROCm GPU visible")
@@ -191,6 +235,7 @@ def main(argv=None, variant="vit"):
     else:
         from model_cnn import IntentNetCNN
         model = IntentNetCNN(backbone_cfg=cfg).to(device)
+    load_initial_weights(model, args, variant, device, log)
     model.set_compute_dtype(torch.bfloat16 if args.dtype == "bf16" else torch.float32)
     loss_fn = DetectionIntentionLoss(use_rotated_iou=USE_ROTATED_IOU, intention_class_weights=None,
                                      apply_intention_downsampling=APPLY_INTENTION_DOWNSAMPLING,

@@ -7,6 +7,7 @@ Compute runs in ``ops.PatchEmbedFn`` / ``PatchEmbedGenericFn`` + ``ops.ViTBlockP
 from __future__ import annotations
 
 import math
+import os
 
 import torch
 import torch.nn as nn
@@ -151,6 +152,45 @@ class VisionTransformer(nn.Module):
     def _cdt(self):
         return BF16 if self.compute_dtype == torch.bfloat16 else F32
 
+    def load_pretrained(self, path_or_state_dict, old_grid=None):
+        """Load a timm checkpoint of this architecture (a ``.pth`` / ``.bin`` / ``.pt`` file through
+        ``torch.load(weights_only=True)``, a ``.safetensors`` file, or a state dict) whatever grid and
+        input channels it was trained at: checkpoint_filter_fn, then ``load_state_dict(strict=True)``.
+        ``old_grid``: the file's patch grid when it is not square. The parameters are written in
+        place, so their version counters move and the bf16 shadows and weight packs kept in ``ops``
+        rebuild at the next forward. Returns what was done: {'file', 'old_grid', 'new_grid',
+        'in_chans'} (old_grid / in_chans None where nothing had to change)."""
+        if isinstance(path_or_state_dict, dict):
+            sd, name = path_or_state_dict, None
+        else:
+            name = str(path_or_state_dict)
+            sd = _load_file(name)
+        sd, info = _filter_state_dict(sd, self, old_grid)
+        self.load_state_dict(sd, strict=True)
+        info["file"] = name
+        return info
+
+    def set_input_size(self, img_size):
+        """timm's VisionTransformer.set_input_size: move the stream to another input size. pos_embed
+        is REPLACED by a new Parameter, its patch rows resampled onto the new grid
+        (resample_abs_pos_embed; the prefix rows keep their bits), and patch_embed.img_size /
+        grid_size / num_patches follow. Call it before an optimizer or a ModelEMA is built on the
+        model: both hold the old Parameter and would go on updating it."""
+        img_size = (int(img_size[0]), int(img_size[1]))
+        pe = self.patch_embed
+        p = pe.patch_size[0]
+        new_grid = (img_size[0] // p, img_size[1] // p)
+        if new_grid[0] < 1 or new_grid[1] < 1:
+            raise ValueError(f"set_input_size: {img_size} holds no patch of size {p}")
+        if new_grid != tuple(pe.grid_size):
+            new = resample_abs_pos_embed(self.pos_embed.detach(), new_grid, old_size=tuple(pe.grid_size),
+                                         num_prefix_tokens=self.num_prefix_tokens)
+            self.pos_embed = nn.Parameter(new, requires_grad=self.pos_embed.requires_grad)
+        pe.img_size = img_size
+        pe.grid_size = new_grid
+        pe.num_patches = new_grid[0] * new_grid[1]
+        self._keep_cache = None
+
     def forward_tokens(self, x):
         """Patch embed + all blocks, without the final norm: (B*(Np+1), D) f32 residual stream."""
         steps = self.forward_tokens_steps(x)
@@ -266,11 +306,154 @@ class VisionTransformer(nn.Module):
         return self.head(self.forward_features(x)[:, 0])
 
 
-def create_model(model_name, pretrained=False, in_chans=3, img_size=(224, 224), drop_path_rate=0.0, **_):
-    """timm.create_model surface used by the reference (model_vit.py:64,71)."""
-    if pretrained:
-        raise RuntimeError("pretrained weights are not available offline; pass pretrained=False")
+def _op_device(device):
+    """Where the two load-time ops (ops.pos_resample, ops.adapt_input_conv) run for a model on
+    ``device``: the model's own GPU, or, for a model still on the host (create_model builds there,
+    like timm), the current GPU; the results go back to wherever the model lives. Without a GPU
+    there is nothing to run them on: no CPU fallback."""
+    device = torch.device(device)
+    if device.type == "cuda":
+        return device
+    if not torch.cuda.is_available():
+        raise RuntimeError("resampling pos_embed / adapting patch_embed weights runs on the GPU kernels "
+                           "(no CPU fallback): no ROCm device visible")
+    return torch.device("cuda", torch.cuda.current_device())
+
+
+def resample_abs_pos_embed(posemb, new_size, old_size=None, num_prefix_tokens=1, interpolation="bicubic",
+                           antialias=True, verbose=False):
+    """timm.layers.resample_abs_pos_embed: the patch rows of ``posemb`` (1, prefix + gh * gw, D)
+    resampled from the ``old_size`` grid onto ``new_size`` (bicubic, antialiased: ops.pos_resample),
+    the prefix rows copied bit for bit. ``old_size=None``: the square grid of the patch-token count.
+    Equal sizes return ``posemb`` itself. Only interpolation='bicubic' with antialias=True (timm's
+    defaults, what checkpoint_filter_fn uses) is built. The result is f32 on posemb's device."""
+    if interpolation != "bicubic" or not antialias:
+        raise ValueError(f"resample_abs_pos_embed: only interpolation='bicubic' with antialias=True is implemented "
+                         f"(got {interpolation!r}, antialias={antialias})")
+    new_size = (int(new_size[0]), int(new_size[1]))
+    n_patch = posemb.shape[1] - num_prefix_tokens
+    if old_size is None:
+        hw = math.isqrt(max(n_patch, 0))
+        if hw * hw != n_patch:
+            raise ValueError(f"resample_abs_pos_embed: {n_patch} patch tokens are not a square grid; pass old_size")
+        old_size = (hw, hw)
+    old_size = (int(old_size[0]), int(old_size[1]))
+    if old_size[0] * old_size[1] != n_patch:
+        raise ValueError(f"resample_abs_pos_embed: old_size {old_size} does not hold {n_patch} patch tokens")
+    if old_size == new_size:
+        return posemb
+    with torch.no_grad():
+        src = posemb.detach()
+        dev = _op_device(src.device)
+        D = src.shape[-1]
+        grid = ops.pos_resample(src[0, num_prefix_tokens:].to(dev).reshape(old_size[0], old_size[1], D), new_size)
+        out = torch.empty((1, num_prefix_tokens + new_size[0] * new_size[1], D), dtype=torch.float32, device=src.device)
+        out[0, :num_prefix_tokens] = src[0, :num_prefix_tokens]
+        out[0, num_prefix_tokens:] = grid.reshape(-1, D).to(src.device)
+    return out
+
+
+def adapt_input_conv(in_chans, conv_weight):
+    """timm adapt_input_conv (its argument order): 3-channel patch-embedding weights for ``in_chans``
+    input channels (ops.adapt_input_conv). f32, on conv_weight's device."""
+    dev = _op_device(conv_weight.device)
+    return ops.adapt_input_conv(conv_weight.detach().to(dev), in_chans).to(conv_weight.device)
+
+
+_DROP_PREFIXES = ("head.", "fc_norm.", "pre_logits.", "head_dist.")
+
+
+def _filter_state_dict(state_dict, model, old_grid=None):
+    """checkpoint_filter_fn and what it did: (state dict, {'old_grid', 'new_grid', 'in_chans'})
+    with 'old_grid' / 'in_chans' None where nothing was resampled / adapted."""
+    for wrap in ("model", "state_dict", "model_state_dict"):
+        if wrap in state_dict and isinstance(state_dict[wrap], dict):
+            state_dict = state_dict[wrap]
+            break
+    own = model.state_dict()
+    dev = model.pos_embed.device
+    new_grid = tuple(model.patch_embed.grid_size)
+    info = {"old_grid": None, "new_grid": new_grid, "in_chans": None}
+    out = {}
+    for k, v in state_dict.items():
+        if k.startswith(_DROP_PREFIXES) and k not in own:
+            continue
+        if k == "pos_embed" and v.dim() == 3:
+            grid = tuple(old_grid) if old_grid is not None else None
+            if v.shape[1] != model.pos_embed.shape[1] or (grid is not None and grid != new_grid):
+                if grid is None:
+                    hw = math.isqrt(max(v.shape[1] - model.num_prefix_tokens, 0))
+                    grid = (hw, hw)  # resample_abs_pos_embed refuses a count that is no square
+                v = resample_abs_pos_embed(v.to(_op_device(dev)), new_grid, old_size=old_grid,
+                                           num_prefix_tokens=model.num_prefix_tokens)
+                info["old_grid"] = grid
+        elif k == "patch_embed.proj.weight" and v.dim() == 4:
+            w = model.patch_embed.proj.weight
+            if tuple(v.shape[2:]) != tuple(w.shape[2:]):
+                raise ValueError(f"checkpoint_filter_fn: patch size {tuple(v.shape[2:])} of the file does not match "
+                                 f"the stream's patch size {tuple(w.shape[2:])} (resample_patch_embed is not built)")
+            if v.shape[1] != w.shape[1]:
+                info["in_chans"] = (int(v.shape[1]), int(w.shape[1]))
+                v = adapt_input_conv(w.shape[1], v.to(_op_device(dev)))
+        out[k] = v
+    return out, info
+
+
+def checkpoint_filter_fn(state_dict, model, old_grid=None):
+    """timm vision_transformer.checkpoint_filter_fn for a stream: unwrap a top-level 'model' /
+    'state_dict' / 'model_state_dict'; drop the classifier keys the stream does not have (head.*,
+    fc_norm.*, pre_logits.*); resample pos_embed onto the stream's grid when the token counts differ
+    (``old_grid``: the file's (gh, gw) when it is not square; given, it also decides between two
+    grids of the same count); adapt patch_embed.proj.weight to the stream's input channels. A
+    patch-size mismatch is a ValueError. Every other tensor passes through as the same object."""
+    return _filter_state_dict(state_dict, model, old_grid)[0]
+
+
+def _load_file(path):
+    path = str(path)
+    if path.endswith(".safetensors"):
+        try:
+            from safetensors.torch import load_file
+        except ImportError as e:
+            raise RuntimeError(f"{path}: reading .safetensors needs the safetensors package, which does not import "
+                               f"({e}); convert the file to .pth") from e
+        return load_file(path, device="cpu")
+    return torch.load(path, map_location="cpu", weights_only=True)
+
+
+PRETRAINED_DIR_ENV = "IVIT_PRETRAINED_DIR"
+
+
+def _pretrained_file(model_name, overlay):
+    """The weight file of create_model(pretrained=True): pretrained_cfg_overlay['file'] (timm's
+    offline route), else $IVIT_PRETRAINED_DIR/<model_name>.safetensors | .pth | .bin."""
+    if overlay and overlay.get("file"):
+        return str(overlay["file"])
+    root = os.environ.get(PRETRAINED_DIR_ENV)
+    tried = []
+    if root:
+        for ext in (".safetensors", ".pth", ".bin"):
+            cand = os.path.join(root, model_name + ext)
+            if os.path.isfile(cand):
+                return cand
+            tried.append(cand)
+    raise RuntimeError(f"pretrained=True for {model_name}: nothing is downloaded; give the weight file as "
+                       f"pretrained_cfg_overlay={{'file': PATH}}, or set {PRETRAINED_DIR_ENV} to a directory holding "
+                       f"{model_name}.safetensors, .pth or .bin"
+                       + (f" (looked for {', '.join(tried)})" if tried else f" ({PRETRAINED_DIR_ENV} is not set)"))
+
+
+def create_model(model_name, pretrained=False, in_chans=3, img_size=(224, 224), drop_path_rate=0.0,
+                 pretrained_cfg_overlay=None, **_):
+    """timm.create_model surface used by the reference (model_vit.py:64,71). ``pretrained=True``
+    loads a timm checkpoint of ``model_name`` from a local file (_pretrained_file) through
+    VisionTransformer.load_pretrained: pos_embed resampled onto ``img_size``'s grid, the 3-channel
+    patch weights adapted to ``in_chans``."""
     a = VIT_ARCH[model_name]
-    return VisionTransformer(img_size=img_size, patch_size=a["patch"], in_chans=in_chans, embed_dim=a["embed_dim"],
-                             depth=a["depth"], num_heads=a["num_heads"], mlp_ratio=a["mlp_ratio"],
-                             drop_path_rate=drop_path_rate)
+    file = _pretrained_file(model_name, pretrained_cfg_overlay) if pretrained else None
+    m = VisionTransformer(img_size=img_size, patch_size=a["patch"], in_chans=in_chans, embed_dim=a["embed_dim"],
+                          depth=a["depth"], num_heads=a["num_heads"], mlp_ratio=a["mlp_ratio"],
+                          drop_path_rate=drop_path_rate)
+    if file is not None:
+        m.load_pretrained(file)
+    return m
