@@ -647,6 +647,55 @@ int ivit_intent_labels(const long* ts, const double* xy, const double* quat, con
                        const long* track_off, long n, long n_tracks, const ivit_label_params* params, int* intent,
                        double* yaw, void* stream);
 
+/* ---- Masked-autoencoder pre-training (He et al. 2021; mae.py, pretrain_mae.py) -----------------
+ * All index arrays are int32 device arrays; nothing here reads device data on the host. D is a
+ * multiple of 64; src / dst / fill / add are 16-byte aligned f32.
+ *
+ * ivit_token_select: dst[b][j][:] = (0 <= idx[b][j] < Ns ? src[b][idx[b][j]][:]
+ *                                                        : (fill ? fill[:] : 0)) + (add ? add[j][:] : 0)
+ * src [B, Ns, D], idx [B, Nd], fill [D] or null, add [Nd, D] or null, dst [B, Nd, D]. An index outside
+ * [0, Ns) means "no source row": src is never read outside its B * Ns rows whatever idx holds. Without
+ * `add` the row is a bit copy; with it, one f32 add per element. The one form is (a) the encoder-side
+ * gather of CLS + the kept patches, (b) its backward through the inverse index (-1 for a dropped
+ * patch: zeros in the same launch, no memset, no atomics), (c) the decoder-side un-shuffle (fill = the
+ * mask token, add = the decoder's position table) and (d) the pick of the masked rows for the
+ * prediction head, and its backward. The backward forms need idx injective on its in-range entries.
+ *
+ * ivit_token_fill_grad: dfill[d] (+)= sum over (b, j) with idx[b][j] outside [0, Ns) of dy[b][j][d]:
+ * the mask token's gradient. dy [B, Nd, D] f32. Partials per 64-row block, then one fixed-order column
+ * pass: no float atomics, bitwise repeatable. accumulate != 0 adds to dfill. work: 4-B aligned,
+ * >= ivit_token_fill_grad_workspace bytes (0 for sizes the entry refuses).
+ *
+ * ivit_mae_loss_fwd / _bwd: mean squared error of the predicted masked patches against the raster.
+ * pred [B*Nm, C*P*P] (pred_dtype IVIT_F32 or IVIT_BF16, 16-byte aligned), img [B, C, H, W] f32
+ * (16-byte aligned; H and W multiples of P, P = 8 or 16), pidx [B, Nm]: the masked patches' indices
+ * into the (H/P) x (W/P) grid, row-major. COLUMN ORDER: column (c*P + ky)*P + kx of pred row
+ * (b, m) is compared with img[b][c][gy*P + ky][gx*P + kx], (gy, gx) = divmod(pidx[b][m], W/P): the
+ * (c, ky, kx) order of ivit_patch_im2col_p and of patch_embed.proj.weight.reshape(D, -1), NOT the
+ * (ky, kx, c) order of the MAE paper's code (its patchify ends in 'nhwpqc'). The target is read out
+ * of the raster; no patch matrix exists. With norm_pix != 0 the target of a patch is
+ * (t - mean) / sqrt(var + 1e-6), var the unbiased (n - 1) variance over the patch's L = C*P*P values
+ * (torch.var); an all-zero patch gives an all-zero target. The forward writes patch_loss [B*Nm] (the
+ * mean over L of the squared difference), stats [B*Nm, 2] = (mean, rstd) per patch ((0, 1) without
+ * norm_pix), loss [1] (the mean over the B*Nm patches, summed in a fixed order in f64) and finite [1]
+ * (f32 1.0 / 0.0: every per-patch loss and the total finite; the flag FusedAdamW.step takes). A pidx
+ * entry outside the grid reads nothing, gives that patch a NaN loss and so finite = 0. The backward
+ * reads the upstream scalar gout [1] and finite [1] from device memory and writes
+ * dpred = gout * 2 (pred - target) / (B*Nm*L) in pred's dtype (16-byte aligned), all zeros when
+ * finite is 0. work: 8-B aligned, >= ivit_mae_loss_workspace bytes. */
+int ivit_token_select(const float* src, long B, long Ns, long D, const int* idx, long Nd, const float* fill,
+                      const float* add, float* dst, void* stream);
+long ivit_token_fill_grad_workspace(long B, long Nd, long D);
+int ivit_token_fill_grad(const float* dy, long B, long Nd, long D, const int* idx, long Ns, float* dfill,
+                         int accumulate, void* work, long work_bytes, void* stream);
+long ivit_mae_loss_workspace(long B, long Nm);
+int ivit_mae_loss_fwd(const void* pred, int pred_dtype, const float* img, long B, long C, long H, long W, long P,
+                      const int* pidx, long Nm, int norm_pix, float* patch_loss, float* stats, float* loss,
+                      float* finite, void* work, long work_bytes, void* stream);
+int ivit_mae_loss_bwd(const void* pred, int pred_dtype, const float* img, long B, long C, long H, long W, long P,
+                      const int* pidx, long Nm, const float* stats, const float* gout, const float* finite,
+                      void* dpred, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -12,6 +12,8 @@ Granularity (fused for HBM traffic and launch count, coarse enough for DDP overl
   * ``NeckFn``        final norms + adapters + fusion BasicBlocks + heads
                       (model_vit.py:116-142, 179-185; heads.py)
   * ``DetLossFn``     DetectionIntentionLoss                        (loss.py:58-206)
+  * ``TokenSelectFn`` / ``PredLinearFn`` / ``MaeLossFn``  the token gather / un-shuffle, prediction
+                      head and reconstruction loss of MAE pre-training (mae.py; no reference code)
 plus single-op Functions used by the standalone module forwards.
 """
 from __future__ import annotations
@@ -1189,3 +1191,135 @@ class DetLossFn(torch.autograd.Function):
                               cfg["beta"], cfg["w_cls"], cfg["w_box"], cfg["w_int"], ptr(stats), ptr(g), ptr(dcls),
                               ptr(dbox), ptr(dint), ptr(ws), ws.numel(), stream())
         return dcls, dbox, dint, None, None, None, None, None, None
+
+
+# ------------------------------------------------------------------------------ MAE pre-training
+def _idx32(idx, B, Nd):
+    if idx.dtype != torch.int32 or tuple(idx.shape) != (B, Nd):
+        raise ValueError(f"token index: expected int32 [{B}, {Nd}], got {idx.dtype} {tuple(idx.shape)}")
+    return idx.contiguous()
+
+
+def token_select(src, B, Ns, idx, fill=None, add=None):
+    """dst[b][j] = (src[b][idx[b][j]] if 0 <= idx[b][j] < Ns else fill or 0) + (add[j] if add) over
+    f32 rows (ivit_token_select). src [B*Ns, D], idx int32 [B, Nd], fill [D], add [Nd, D] -> [B*Nd, D]."""
+    D = src.shape[-1]
+    Nd = idx.shape[1]
+    idx = _idx32(idx, B, Nd)
+    src = src.contiguous()
+    dst = torch.empty((B * Nd, D), dtype=torch.float32, device=src.device)
+    lib.ivit_token_select(ptr(src), B, Ns, D, ptr(idx), Nd, ptr(fill), ptr(add), ptr(dst), stream())
+    return dst
+
+
+def token_fill_grad(dy, B, idx, Ns, out=None, accumulate=False):
+    """The fill row's gradient of token_select: the column sum of the rows of dy [B*Nd, D] whose idx
+    is outside [0, Ns) (ivit_token_fill_grad; fixed summation order). -> f32 [D] (``out``, added to
+    when ``accumulate``)."""
+    D = dy.shape[-1]
+    Nd = idx.shape[1]
+    idx = _idx32(idx, B, Nd)
+    dy = dy.contiguous()
+    out = torch.empty((D,), dtype=torch.float32, device=dy.device) if out is None else out
+    ws = workspace(lib.ivit_token_fill_grad_workspace(B, Nd, D), dy.device)
+    lib.ivit_token_fill_grad(ptr(dy), B, Nd, D, ptr(idx), Ns, ptr(out), int(bool(accumulate)), ptr(ws), ws.numel(),
+                             stream())
+    return out
+
+
+class TokenSelectFn(torch.autograd.Function):
+    """token_select with its backward: the source gradient is the same kernel through ``inv``
+    (int32 [B, Ns]: the destination row that took source row s, -1 where none did; idx must be
+    injective on its in-range entries), the fill gradient ivit_token_fill_grad. ``add`` is a constant
+    table (the decoder's fixed sin-cos positions)."""
+
+    @staticmethod
+    def forward(ctx, src, idx, inv, fill, add, B, Ns):
+        ctx.save_for_backward(idx, inv)
+        ctx.meta = (B, Ns, idx.shape[1], fill is not None, None if fill is None else fill.shape)
+        f = None if fill is None else fill.detach().reshape(-1).float().contiguous()
+        return token_select(src.float(), B, Ns, idx, fill=f, add=add)
+
+    @staticmethod
+    def backward(ctx, dy):
+        idx, inv = ctx.saved_tensors
+        B, Ns, Nd, has_fill, fshape = ctx.meta
+        dy = dy.float().contiguous()
+        dsrc = token_select(dy, B, Nd, inv) if ctx.needs_input_grad[0] else None
+        dfill = None
+        if has_fill and ctx.needs_input_grad[3]:
+            dfill = token_fill_grad(dy, B, idx, Ns).reshape(fshape)
+        return dsrc, None, None, dfill, None, None, None
+
+
+class PredLinearFn(torch.autograd.Function):
+    """The MAE prediction head: x [M, K] f32 -> x w^T + b in the COMPUTE dtype (bf16 pred rows halve
+    the largest tensor of the step; the loss kernel reads either), on the generic GEMM."""
+
+    @staticmethod
+    def forward(ctx, x, w, b, cdt):
+        cd = tdtype(cdt)
+        x2 = cast(x.contiguous(), cd)
+        wc = cast_weight(w, cd)
+        y, _ = linear_fwd(x2, wc, b, cdt, out_dtype=cd)
+        ctx.save_for_backward(x2, wc)
+        ctx.cdt = cdt
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        x2, wc = ctx.saved_tensors
+        d2 = cast(dy.contiguous(), tdtype(ctx.cdt))
+        dx = linear_dgrad(d2, wc, ctx.cdt, torch.float32)
+        dw, db = linear_wgrad(d2, x2, ctx.cdt)
+        return dx, dw, db, None
+
+
+def mae_loss_fwd(pred, img, pidx, P, norm_pix):
+    """-> (loss [1], finite [1], patch_loss [B*Nm], stats [B*Nm, 2]) (ivit_mae_loss_fwd)."""
+    B, C, H, W = img.shape
+    Nm = pidx.shape[1]
+    pidx = _idx32(pidx, B, Nm)
+    if tuple(pred.shape) != (B * Nm, C * P * P) or not pred.is_contiguous():
+        raise ValueError(f"mae_loss: pred {tuple(pred.shape)} is not the contiguous [{B * Nm}, {C * P * P}]")
+    dev = pred.device
+    pl = torch.empty((B * Nm,), dtype=torch.float32, device=dev)
+    st = torch.empty((B * Nm, 2), dtype=torch.float32, device=dev)
+    out = torch.empty((2,), dtype=torch.float32, device=dev)
+    ws = workspace(lib.ivit_mae_loss_workspace(B, Nm), dev)
+    lib.ivit_mae_loss_fwd(ptr(pred), dt(pred), ptr(img), B, C, H, W, P, ptr(pidx), Nm, int(bool(norm_pix)), ptr(pl),
+                          ptr(st), ptr(out), out.data_ptr() + 4, ptr(ws), ws.numel(), stream())
+    return out[0:1], out[1:2], pl, st
+
+
+def mae_loss_bwd(pred, img, pidx, P, stats, gout, finite):
+    B, C, H, W = img.shape
+    Nm = pidx.shape[1]
+    dpred = torch.empty_like(pred)
+    lib.ivit_mae_loss_bwd(ptr(pred), dt(pred), ptr(img), B, C, H, W, P, ptr(pidx), Nm, ptr(stats), ptr(gout),
+                          ptr(finite), ptr(dpred), stream())
+    return dpred
+
+
+class MaeLossFn(torch.autograd.Function):
+    """Masked-patch reconstruction loss (ivit_mae_loss_*): pred [B*Nm, C*P*P] (f32 / bf16) against
+    the raster img [B, C, H, W] at the patches pidx int32 [B, Nm]. -> (loss 0-d, finite [1] f32
+    1.0 / 0.0, per-patch loss [B*Nm]); the backward writes exact zeros when finite is 0."""
+
+    @staticmethod
+    def forward(ctx, pred, img, pidx, P, norm_pix):
+        img = img.float().contiguous()
+        loss, finite, pl, stats = mae_loss_fwd(pred, img, pidx, P, norm_pix)
+        ctx.save_for_backward(pred, img, pidx, stats, finite)
+        ctx.P = P
+        ctx.mark_non_differentiable(finite, pl)
+        ctx.set_materialize_grads(False)
+        return loss.clone().reshape(()), finite, pl
+
+    @staticmethod
+    def backward(ctx, gloss, *_unused):
+        pred, img, pidx, stats, finite = ctx.saved_tensors
+        if gloss is None:
+            return None, None, None, None, None
+        g = gloss.reshape(1).float().contiguous()
+        return mae_loss_bwd(pred, img, pidx, ctx.P, stats, g, finite), None, None, None, None
