@@ -257,10 +257,19 @@ def _ln_scales(ref):
     return s
 
 
-def ln_case(family, M, D, eps, rowmap=(0, 0, 0), dy_bf16=False, with_dres=True, row_scale=None, rps=1, seed=0):
+def ln_case(family, M, D, eps, rowmap=(0, 0, 0), dy_bf16=False, with_dres=True, row_scale=None, rps=1, seed=0,
+            X=None, dy=None):
     """One LayerNorm case: inputs, the f64 reference, torch's f32 figures and the tolerances.
-    row_scale: a tuple of per-sample scales (or None)."""
+    row_scale: a tuple of per-sample scales (or None). X, dy: given tensors in place of the family's
+    (a fused GEMM's exact product as the LayerNorm input or as the incoming gradient)."""
+    given_x, given_dy = X, dy
     X, gamma, beta, dy, dres = ln_inputs(family, M, D, rowmap, seed)
+    if given_x is not None:
+        assert given_x.shape == X.shape
+        X = given_x.float()
+    if given_dy is not None:
+        assert given_dy.shape == dy.shape
+        dy = given_dy.float()
     if dy_bf16:
         dy = bf16_exact(dy)
     if not with_dres:

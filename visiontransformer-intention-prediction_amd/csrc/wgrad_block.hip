@@ -144,7 +144,7 @@ __global__ __launch_bounds__(512, 1) void wgrad_block_kernel(const WbArgs args) 
     wait_step(0);
     __builtin_amdgcn_s_barrier();  // B_0
     if (3 < nk) issue(3, kbeg + 3 * WB_BK);
-    if (dob) bias(0);
+    if (dob && nk > 0) bias(0);  // a split past M has no step 0: stage 0 was never written
     for (int j = 1; j <= nk; ++j) {
       if (j < nk) wait_step(j);
       asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // my bias reads of stage j - 1 are done
@@ -297,9 +297,13 @@ extern "C" int ivit_vit_block_wgrad(long M, long D, long Hd, const void* dy2, co
   const void* outs[8] = {dw2, db2, dw1, db1, dwp, dbp, dwq, dbq};
   for (int i = 0; i < 8; ++i)
     IVIT_CHECK_ARG(((uintptr_t)outs[i] & 15) == 0, "ivit_vit_block_wgrad: output %d not 16-B aligned", i);
-  const int S = wb_splits(M);
+  // only the non-empty splits are launched and reduced: with ceil(steps / wb_splits) steps per
+  // split, 6 * that can reach past the last step (steps 8 .. 12, 15 .. 18, ...); S <= wb_splits(M),
+  // so the workspace bound holds
   const long steps = (M + WB_BK - 1) / WB_BK;
-  const int kchunk = (int)((steps + S - 1) / S) * WB_BK;
+  const long csteps = (steps + wb_splits(M) - 1) / wb_splits(M);
+  const int S = (int)((steps + csteps - 1) / csteps);
+  const int kchunk = (int)csteps * WB_BK;
   WbArgs args;
   // (dY, X, N, K): fc2 dY = dx2s [M][D], X = gelu output [M][Hd]; fc1 dY = dh [M][Hd], X = ln2;
   // proj dY = dx1s, X = attention output; qkv dY = dqkv [M][3D], X = ln1
