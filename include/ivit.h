@@ -394,6 +394,27 @@ int ivit_adamw_chunked_ema(long n_tensors, void* const* params, void* const* gra
                            float bc1, float bc2_sqrt, const float* finite, const float* steps_in, float* steps_out,
                            const float* grad_scale, void* const* emas, double ema_decay, int ema_warmup,
                            void* stream);
+/* ivit_adamw_chunked_ema with a per-tensor hyper-parameter table, so that parameter groups which
+ * differ only in learning-rate scale and weight decay (layer-wise lr decay, no decay on 1-D tensors)
+ * share ONE launch: hyper (device f32 [n_tensors][2], 8-B aligned; null = ivit_adamw_chunked_ema,
+ * bit-identical) = (lr_scale, weight_decay) of tensor t. Each workgroup reads its tensor's pair once
+ * and forms, in f32, before the element loop
+ *   lr_t = lr * hyper[t][0]                      one multiply, never fused
+ *   keep = fma(-lr_t, hyper[t][1], 1)            p *= keep; ONE rounding, as 1 - lr * wd is formed
+ *                                                in the launches above
+ *   step = lr_t / bc1                            p -= step * m / (sqrt(v) / bc2_sqrt + eps)
+ * so the update of tensor t is, bit for bit, the one ivit_adamw_chunked_ema makes with
+ * lr = (float)lr * (float)lr_scale and weight_decay = hyper[t][1], and a host that repeats the three
+ * lines on stored values gets the same bits. lr_scale 0 leaves the parameter (and its shadow) as it
+ * is while the moments, the count and the average move. The scalar weight_decay is
+ * ignored. lr must be finite and >= 0. Everything else (finite, device step counts, f64 bias
+ * correction, grad_scale, emas with warmup, shadows) is ivit_adamw_chunked_ema's. */
+int ivit_adamw_chunked_pt(long n_tensors, void* const* params, void* const* grads, void* const* exp_avg,
+                          void* const* exp_avg_sq, void* const* shadows, const long* sizes, const int* chunks,
+                          long n_chunks, float lr, double beta1, double beta2, float eps, float weight_decay,
+                          float bc1, float bc2_sqrt, const float* finite, const float* steps_in, float* steps_out,
+                          const float* grad_scale, void* const* emas, double ema_decay, int ema_warmup,
+                          const float* hyper, void* stream);
 /* a[t] <-> b[t] (f32, sizes[t] elements) exchanged in place over the same chunk grid, no third
  * buffer; shadows (may be null or hold null entries) receives bf16 of the new a[t]. Puts the averaged
  * weights into the model and back (optim.ModelEMA.swapped). */

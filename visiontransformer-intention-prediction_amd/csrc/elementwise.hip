@@ -192,6 +192,14 @@ __global__ __launch_bounds__(256) void adamw_kernel(void* const* params, void* c
 // (device counts only: without them the host knows n and passes the step's d as ema_decay). It sits
 // behind the finite exit like the pow of the bias corrections, so a skipped launch pays for neither
 // and leaves e alone. The EMA = false instantiations are the kernels as they were.
+// PT (ivit_adamw_chunked_pt): hyper[t] = (lr_scale, weight_decay) of tensor t, a device f32 [n][2] table
+// that lets parameter groups which differ only in those two share the launch (layer-wise lr decay, no
+// decay on 1-D tensors). It is uniform over the workgroup and read once, before the element loop:
+//   lr_t = lr * hyper[t].x ; keep = fma(-lr_t, hyper[t].y, 1) ; step = lr_t / bc1
+// lr_t is the rounded f32 product a host forms for a per-group launch, and keep is the single-rounding
+// form 1 - lr * wd has in the PT = false kernels (the backend contracts it there; written out here, so
+// the table launch and a launch per group give the same bits). The scalar wd is not read. The
+// PT = false instantiations are the kernels as they were.
 constexpr int AW_CHUNK = 4096;
 IVIT_DEV float scaled_grad(float g, float s) {
 #pragma clang fp contract(off)
@@ -203,7 +211,11 @@ IVIT_DEV float ema_elem(float e, float p, float omd) {
   const float mv = omd * diff;
   return e + mv;
 }
-template <bool SCALED, bool EMA>
+IVIT_DEV float scaled_lr(float lr, float s) {
+#pragma clang fp contract(off)
+  return lr * s;
+}
+template <bool SCALED, bool EMA, bool PT = false>
 __global__ __launch_bounds__(256) void adamw_chunk_kernel(void* const* params, void* const* grads, void* const* ms,
                                                           void* const* vs, const long* sizes, const int2* chunks,
                                                           float lr, float b2, float eps, float wd, float bc1,
@@ -211,9 +223,14 @@ __global__ __launch_bounds__(256) void adamw_chunk_kernel(void* const* params, v
                                                           const float* steps_in, float* steps_out, double b1d,
                                                           double b2d, float omb1, float omb2,
                                                           const float* grad_scale, void* const* emas,
-                                                          double ema_decay, int ema_warmup) {
+                                                          double ema_decay, int ema_warmup,
+                                                          const float2* hyper = nullptr) {
   const int2 ck = chunks[blockIdx.x];
   const int t = ck.x;
+  // PT: this tensor's (lr_scale, weight_decay), read ahead of the count store below so that it stays
+  // a scalar load (uniform over the workgroup, once per workgroup)
+  float2 hy = make_float2(1.f, 0.f);
+  if constexpr (PT) hy = hyper[t];
   const bool go = finite == nullptr || *finite != 0.f;
   double nstep = 0.0;  // EMA: the count after this update (device counts)
   if (steps_in != nullptr) {
@@ -245,7 +262,14 @@ __global__ __launch_bounds__(256) void adamw_chunk_kernel(void* const* params, v
   bf16* sh = shadows && shadows[t] ? (bf16*)shadows[t] + off : nullptr;
   float* ea = nullptr;
   if constexpr (EMA) ea = emas[t] ? (float*)emas[t] + off : nullptr;
-  const float step = lr / bc1, keep = 1.f - lr * wd;
+  float step, keep;
+  if constexpr (PT) {
+    const float lrt = scaled_lr(lr, hy.x);
+    keep = __builtin_fmaf(-lrt, hy.y, 1.f);
+    step = lrt / bc1;
+  } else {
+    step = lr / bc1, keep = 1.f - lr * wd;
+  }
   float gs = 1.f;
   if constexpr (SCALED) gs = *grad_scale;
   auto upd = [&](float gi, float& pi, float& mi, float& vi) {
@@ -621,6 +645,52 @@ extern "C" int ivit_adamw_chunked_ema(long n_tensors, void* const* params, void*
                        exp_avg_sq, sizes, (const int2*)chunks, lr, (float)beta2, eps, weight_decay, bc1, bc2_sqrt,
                        shadows, finite, steps_in, steps_out, beta1, beta2, (float)(1.0 - beta1), (float)(1.0 - beta2),
                        (const float*)nullptr, emas, ema_decay, ema_warmup);
+  IVIT_LAUNCH_CHECK();
+  return 0;
+}
+
+extern "C" int ivit_adamw_chunked_pt(long n_tensors, void* const* params, void* const* grads, void* const* exp_avg,
+                                     void* const* exp_avg_sq, void* const* shadows, const long* sizes,
+                                     const int* chunks, long n_chunks, float lr, double beta1, double beta2,
+                                     float eps, float weight_decay, float bc1, float bc2_sqrt, const float* finite,
+                                     const float* steps_in, float* steps_out, const float* grad_scale,
+                                     void* const* emas, double ema_decay, int ema_warmup, const float* hyper,
+                                     void* stream) {
+  if (hyper == nullptr)
+    return ivit_adamw_chunked_ema(n_tensors, params, grads, exp_avg, exp_avg_sq, shadows, sizes, chunks, n_chunks, lr,
+                                  beta1, beta2, eps, weight_decay, bc1, bc2_sqrt, finite, steps_in, steps_out,
+                                  grad_scale, emas, ema_decay, ema_warmup, stream);
+  IVIT_CHECK_ARG(((uintptr_t)hyper & 7) == 0, "ivit_adamw_chunked_pt: misaligned hyper table");
+  IVIT_CHECK_ARG(lr >= 0.f && __builtin_isfinite(lr), "ivit_adamw_chunked_pt: lr must be finite and >= 0 (got %g)",
+                 (double)lr);  // NaN fails too
+  if (emas != nullptr) {
+    IVIT_CHECK_ARG(ema_decay >= 0.0 && ema_decay < 1.0, "ivit_adamw_chunked_pt: ema_decay must be in [0, 1) (got %g)",
+                   ema_decay);  // NaN fails too
+    IVIT_CHECK_ARG(!ema_warmup || steps_in != nullptr,
+                   "ivit_adamw_chunked_pt: ema_warmup needs the device step counts (without steps_in the host "
+                   "passes the step's decay as ema_decay)");
+    IVIT_CHECK_ARG(((uintptr_t)emas & 7) == 0, "ivit_adamw_chunked_pt: misaligned ema table");
+  }
+  if (n_tensors <= 0 || n_chunks <= 0) return 0;
+  IVIT_CHECK_ARG(chunks != nullptr && n_chunks < (1L << 31), "ivit_adamw_chunked_pt: bad chunk table");
+  IVIT_CHECK_ARG((steps_in == nullptr) == (steps_out == nullptr), "ivit_adamw_chunked_pt: steps_in / steps_out pair");
+  IVIT_CHECK_ARG(steps_in == nullptr || steps_in != steps_out, "ivit_adamw_chunked_pt: steps_out aliases steps_in");
+  IVIT_CHECK_ARG(((uintptr_t)chunks & 7) == 0, "ivit_adamw_chunked_pt: misaligned chunk table");
+  const dim3 grid((unsigned)n_chunks), block(256);
+#define IVIT_AW_PT(S, E)                                                                                              \
+  hipLaunchKernelGGL((adamw_chunk_kernel<S, E, true>), grid, block, 0, ivit_stream(stream), params, grads, exp_avg,   \
+                     exp_avg_sq, sizes, (const int2*)chunks, lr, (float)beta2, eps, weight_decay, bc1, bc2_sqrt,      \
+                     shadows, finite, steps_in, steps_out, beta1, beta2, (float)(1.0 - beta1), (float)(1.0 - beta2),  \
+                     grad_scale, emas, ema_decay, ema_warmup, (const float2*)hyper)
+  if (grad_scale != nullptr && emas != nullptr)
+    IVIT_AW_PT(true, true);
+  else if (grad_scale != nullptr)
+    IVIT_AW_PT(true, false);
+  else if (emas != nullptr)
+    IVIT_AW_PT(false, true);
+  else
+    IVIT_AW_PT(false, false);
+#undef IVIT_AW_PT
   IVIT_LAUNCH_CHECK();
   return 0;
 }

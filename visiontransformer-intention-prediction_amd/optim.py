@@ -1,9 +1,14 @@
 """Fused AdamW (torch.optim.AdamW semantics as used at train_vit.py:130: lr 1e-4, wd 1e-4,
-betas (0.9, 0.999), eps 1e-8, decoupled weight decay) — one HIP launch per parameter group
-over device pointer tables instead of torch's per-tensor foreach kernels."""
+betas (0.9, 0.999), eps 1e-8, decoupled weight decay) over device pointer tables instead of torch's
+per-tensor foreach kernels: one HIP launch per parameter group, or with ``fuse_groups=True`` ONE
+launch for all groups that share lr, betas and eps (their per-group ``lr_scale`` and ``weight_decay``
+go to the kernel as a per-tensor table). Beside it the fine-tuning recipe those groups are for:
+``layer_decay_param_groups`` (layer-wise lr decay, no decay on 1-D tensors and tokens) and
+``WarmupCosineLR`` (linear warmup, cosine decay, stepped per update)."""
 from __future__ import annotations
 
 import contextlib
+import ctypes
 import math
 
 import torch
@@ -113,6 +118,22 @@ class _Tables:
             self._tables[key] = tab
         return tab
 
+    def _table_hyper(self, runs, device):
+        """Device f32 [n][2] table of (lr_scale, weight_decay) per tensor of an ivit_adamw_chunked_pt
+        launch, from ``runs`` = [(lr_scale, weight_decay, count)]: consecutive tensors with the same pair
+        (a parameter group's). The table holds values only, so the runs are its key: the same groups
+        over other gradient buffers reuse it, and the lr itself is a kernel scalar (a schedule that
+        moves it every step uploads nothing)."""
+        key = ("hyper",) + tuple(runs)
+        tab = self._tables.get(key)
+        if tab is None:
+            rows = [(s, w) for s, w, n in runs for _ in range(n)]
+            tab = torch.tensor(rows, dtype=torch.float32).reshape(len(rows), 2).pin_memory().to(device, non_blocking=True)
+            if len(self._tables) > 64:
+                self._tables.clear()
+            self._tables[key] = tab
+        return tab
+
     def _pack_jobs(self, jobs, device):
         """Device table of ivit_weight_pack_multi records (w, wpack, rows, cols, transposed), 40 B each."""
         key = ("packs",) + tuple(jobs)
@@ -142,9 +163,29 @@ class GradNorm:
 STATS_FIELDS = ("steps", "clipped", "nonfinite", "norm_sum", "norm_max")  # ivit_grad_norm's stats (f64 [5])
 
 
+def _f32(x):
+    return ctypes.c_float(x).value
+
+
+def effective_lr(lr, lr_scale):
+    """f32(lr) * f32(lr_scale) rounded to f32: the learning rate of a group with ``lr_scale``, as the
+    per-group launch receives it and as ivit_adamw_chunked_pt forms it from its table."""
+    return _f32(_f32(lr) * _f32(lr_scale))  # the f64 product of two f32 values is exact: one rounding
+
+
 class FusedAdamW(torch.optim.Optimizer, _Tables):
-    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2):
+    """``lr_scale`` (optional per group, the timm key; absent = 1): the group's learning rate is
+    ``effective_lr(group['lr'], group['lr_scale'])``; it is part of ``state_dict()`` like every other
+    group entry. ``fuse_groups=False``: one launch per group (a group without ``lr_scale`` makes exactly
+    the call it always made). ``fuse_groups=True``: the groups that share lr, betas and eps go out in
+    ONE ivit_adamw_chunked_pt launch (per distinct step count when the host counts, as within a group)
+    with their (lr_scale, weight_decay) in a per-tensor table, followed by one ivit_weight_pack_multi
+    over all their packs; groups that differ in lr, betas or eps launch separately. Bit-identical to
+    the per-group form."""
+
+    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2, fuse_groups=False):
         super().__init__(params, dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay))
+        self.fuse_groups = bool(fuse_groups)
         self._tables = {}
 
     @torch.no_grad()
@@ -177,6 +218,7 @@ class FusedAdamW(torch.optim.Optimizer, _Tables):
         if closure is not None:
             with torch.enable_grad():
                 loss = closure()
+        merged = {}  # fuse_groups: (lr, betas, eps) -> [first group, parameters, (lr_scale, weight_decay, count) runs]
         for group in self.param_groups:
             live = [p for p in group["params"] if p.grad is not None]
             for p in live:
@@ -186,22 +228,42 @@ class FusedAdamW(torch.optim.Optimizer, _Tables):
             self._init_state([p for p in live if not self.state[p]])
             if not live:
                 continue
-            if finite is None:
-                by_step = {}
-                for p in live:
-                    st = self.state[p]
-                    st["step"] = int(st["step"]) + 1  # a device count (sync-free path) is read once
-                    by_step.setdefault(st["step"], []).append(p)
-                for step, ps in by_step.items():
-                    b1, b2 = group["betas"]
-                    self._launch(group, ps, 1.0 - b1 ** step, math.sqrt(1.0 - b2 ** step), None, None, None, grad_scale,
-                                 ema, step)
+            if self.fuse_groups:
+                key = (float(group["lr"]), tuple(float(b) for b in group["betas"]), float(group["eps"]))
+                m = merged.setdefault(key, [group, [], []])
+                m[1] += live
+                m[2].append((float(group.get("lr_scale", 1.0)), float(group["weight_decay"]), len(live)))
             else:
-                sin, sout = self._device_steps(live)
-                self._launch(group, live, 1.0, 1.0, finite, sin, sout, grad_scale, ema)
-                for i, p in enumerate(live):
-                    self.state[p]["step"] = sout[i]  # 0-d view; the other buffer is next step's output
+                self._update(group, live, None, finite, grad_scale, ema)
+        for group, live, hyper in merged.values():
+            self._update(group, live, hyper, finite, grad_scale, ema)
         return loss
+
+    def _update(self, group, live, hyper, finite, grad_scale, ema):
+        """The launch(es) of one group's live parameters, or with ``hyper`` (runs of (lr_scale,
+        weight_decay, count) over ``live``) of the merged groups that share ``group``'s lr, betas and eps."""
+        if finite is None:
+            each = None if hyper is None else [(s, w) for s, w, n in hyper for _ in range(n)]
+            by_step = {}
+            for i, p in enumerate(live):
+                st = self.state[p]
+                st["step"] = int(st["step"]) + 1  # a device count (sync-free path) is read once
+                ps, hy = by_step.setdefault(st["step"], ([], []))
+                ps.append(p)
+                if each is not None:
+                    if hy and hy[-1][:2] == each[i]:
+                        hy[-1] = each[i] + (hy[-1][2] + 1,)
+                    else:
+                        hy.append(each[i] + (1,))
+            for step, (ps, hy) in by_step.items():
+                b1, b2 = group["betas"]
+                self._launch(group, ps, 1.0 - b1 ** step, math.sqrt(1.0 - b2 ** step), None, None, None, grad_scale,
+                             ema, step, hy if hyper is not None else None)
+        else:
+            sin, sout = self._device_steps(live)
+            self._launch(group, live, 1.0, 1.0, finite, sin, sout, grad_scale, ema, None, hyper)
+            for i, p in enumerate(live):
+                self.state[p]["step"] = sout[i]  # 0-d view; the other buffer is next step's output
 
     @torch.no_grad()
     def grad_norm(self, max_norm, finite=None, stats=None):
@@ -232,14 +294,16 @@ class FusedAdamW(torch.optim.Optimizer, _Tables):
         self._tables[key] = bufs
         return bufs
 
-    def _launch(self, group, ps, bc1, bc2s, finite, sin, sout, grad_scale=None, ema=None, host_step=None):
+    def _launch(self, group, ps, bc1, bc2s, finite, sin, sout, grad_scale=None, ema=None, host_step=None, hyper=None):
         """The update of ``ps`` through the chunked streaming kernel (live bf16 compute copies,
         ops.cast_weight, rewritten in it), then every live row-panel weight pack (ops.packed_weight /
         packed_weight_t) rebuilt from the updated f32 weights in ONE launch: the pointer-table update
         moves no version counter, so without it the packs would stay at the old weights.
         ``ema`` (ModelEMA): its table goes to ivit_adamw_chunked_ema; with device counts the launch
         forms the decay from steps_in, with host counts (``host_step``: the count after this update)
-        the host does and passes it with the warmup off."""
+        the host does and passes it with the warmup off. ``hyper`` (runs of (lr_scale, weight_decay, count)
+        over ``ps``, fuse_groups): the table of ivit_adamw_chunked_pt, which takes the group's lr as it is;
+        without it a group's ``lr_scale`` is folded into the lr scalar on the host (effective_lr)."""
         b1, b2 = group["betas"]
         dev = ps[0].device
         st = [self.state[p] for p in ps]
@@ -250,10 +314,20 @@ class FusedAdamW(torch.optim.Optimizer, _Tables):
         sizes = self._table_sizes(ps, dev)
         shadows, jobs, big = self._followers(ps)
         chunks, nch = self._table_chunks(ps, dev)
+        lr = group["lr"] if hyper is not None or "lr_scale" not in group else effective_lr(group["lr"], group["lr_scale"])
         args = (len(ps), ptr(tp), ptr(tg), ptr(tm), ptr(tv), ptr(self._table_ptrs(shadows, dev)), ptr(sizes),
-                ptr(chunks), nch, group["lr"], b1, b2, group["eps"], group["weight_decay"], bc1, bc2s, ptr(finite),
+                ptr(chunks), nch, lr, b1, b2, group["eps"], group["weight_decay"], bc1, bc2s, ptr(finite),
                 ptr(sin), ptr(sout))
-        if ema is not None:
+        if hyper is not None:
+            if sum(n for _, _, n in hyper) != len(ps):  # the kernel reads one table row per tensor
+                raise RuntimeError("FusedAdamW: the (lr_scale, weight_decay) runs do not cover the launch's tensors")
+            te, decay, warm = None, 0.0, 0
+            if ema is not None:
+                te = self._table_ptrs(ema._ptrs(ps), dev)
+                decay, warm = (ema.decay, int(ema.warmup)) if sin is not None else (ema.decay_at(host_step), 0)
+            lib.ivit_adamw_chunked_pt(*args, ptr(grad_scale), ptr(te), decay, warm,
+                                      ptr(self._table_hyper(hyper, dev)), stream())
+        elif ema is not None:
             te = self._table_ptrs(ema._ptrs(ps), dev)
             decay, warm = (ema.decay, int(ema.warmup)) if sin is not None else (ema.decay_at(host_step), 0)
             lib.ivit_adamw_chunked_ema(*args, ptr(grad_scale), ptr(te), decay, warm, stream())
@@ -405,3 +479,122 @@ def clip_grad_norm_(parameters, max_norm, norm_type=2.0, error_if_nonfinite=Fals
                            "by the non-finite norm anyway, set `error_if_nonfinite=False`")
     _clip_tables._scale_launch(grads, rec.coef)
     return rec.norm
+
+
+NO_DECAY_NAMES = ("pos_embed", "cls_token", "mask_token", "decoder_pos_embed")
+
+
+def layer_decay_param_groups(model, layer_decay=1.0, weight_decay=0.0, no_decay_1d=True):
+    """Parameter groups for fine-tuning with layer-wise learning-rate decay (the rule of timm's
+    ``param_groups_layer_decay``; BEiT / MAE fine-tuning), for FusedAdamW(..., fuse_groups=True).
+
+    Every vit.VisionTransformer inside ``model`` is a stream of depth L = len(blocks): its
+    ``patch_embed.*``, ``cls_token`` and ``pos_embed`` have layer id 0, ``blocks.i.*`` has id i + 1, and
+    the rest of it (the final ``norm``) the top id L + 1. Everything outside the streams (adapters,
+    fusion block, heads; all of IntentNetCNN) has the top id. A parameter's group carries
+    ``lr_scale = layer_decay ** (L + 1 - id)`` (f64) and ``layer_id``; the top id has scale 1.
+    ``no_decay_1d``: parameters with ndim <= 1, names ending ``.bias``, and ``pos_embed`` / ``cls_token`` /
+    ``mask_token`` / ``decoder_pos_embed`` get ``weight_decay`` 0, the others ``weight_decay``.
+    Parameters with equal (lr_scale, weight_decay) share a group; groups appear in the order of their
+    first parameter in ``model.named_parameters()`` and keep that order inside, so every construction
+    (every DDP rank) builds the same groups. Frozen parameters are left out.
+    ``layer_decay=1, no_decay_1d=False`` is the single group of ``model.parameters()``."""
+    import vit
+    layer_decay, weight_decay = float(layer_decay), float(weight_decay)
+    if not 0.0 < layer_decay <= 1.0:  # NaN fails too
+        raise ValueError(f"layer_decay must be in (0, 1] (got {layer_decay})")
+    streams = [(name + "." if name else "", len(m.blocks)) for name, m in model.named_modules()
+               if isinstance(m, vit.VisionTransformer)]
+    top = max((depth for _, depth in streams), default=0) + 1
+    groups = {}
+    for name, p in model.named_parameters():
+        if not p.requires_grad:
+            continue
+        lid, depth = top, top - 1
+        for prefix, d in streams:
+            if name.startswith(prefix):
+                rest, depth = name[len(prefix):], d
+                if rest in ("cls_token", "pos_embed") or rest.startswith("patch_embed."):
+                    lid = 0
+                elif rest.startswith("blocks."):
+                    lid = int(rest.split(".")[1]) + 1
+                else:
+                    lid = d + 1
+                break
+        scale = layer_decay ** (depth + 1 - lid)
+        leaf = name.rsplit(".", 1)[-1]
+        no_decay = no_decay_1d and (p.ndim <= 1 or name.endswith(".bias") or leaf in NO_DECAY_NAMES)
+        wd = 0.0 if no_decay else weight_decay
+        g = groups.setdefault((scale, wd), {"params": [], "lr_scale": scale, "weight_decay": wd, "layer_id": lid})
+        g["params"].append(p)
+    return list(groups.values())
+
+
+def group_summary(param_groups):
+    """[(layer_id, lr_scale, tensors, elements)] per distinct lr_scale of ``param_groups``, smallest
+    scale first: the lines train_vit.py logs."""
+    rows = {}
+    for g in param_groups:
+        r = rows.setdefault(float(g.get("lr_scale", 1.0)), [0, 0, 0])
+        r[0] = max(r[0], g.get("layer_id", 0))
+        r[1] += len(g["params"])
+        r[2] += sum(p.numel() for p in g["params"])
+    return [(r[0], s, r[1], r[2]) for s, r in sorted(rows.items())]
+
+
+class WarmupCosineLR:
+    """Linear warmup then cosine decay of every group's ``lr``, stepped once per optimiser update.
+    For update k (counted from 0), with W = ``warmup_steps``, T = ``total_steps`` and ``base`` the
+    group's lr at construction (kept as the group's ``initial_lr``), in f64:
+        k < W:  warmup_init_lr + (base - warmup_init_lr) * k / W
+        else:   min_lr + 0.5 * (base - min_lr) * (1 + cos(pi * (k - W) / max(1, T - W))), min_lr once k >= T
+    The constructor writes the lr of update 0; ``step()`` (after each ``optimizer.step``) moves to the
+    next update. A group's ``lr_scale`` is not touched: it multiplies this lr in the optimiser (the
+    kernel's table, with ``fuse_groups``), so a schedule step uploads nothing. The lr is a function of
+    the update index alone, hence the same on every rank. An update the device skips (``finite`` = 0)
+    still advances the schedule: the host does not read the flag."""
+
+    def __init__(self, optimizer, warmup_steps, total_steps, min_lr=0.0, warmup_init_lr=0.0):
+        warmup_steps, total_steps = int(warmup_steps), int(total_steps)
+        if warmup_steps < 0 or total_steps <= 0 or warmup_steps > total_steps:
+            raise ValueError(f"WarmupCosineLR: need 0 <= warmup_steps <= total_steps, total_steps > 0 "
+                             f"(got {warmup_steps}, {total_steps})")
+        self.optimizer = optimizer
+        self.warmup_steps, self.total_steps = warmup_steps, total_steps
+        self.min_lr, self.warmup_init_lr = float(min_lr), float(warmup_init_lr)
+        # torch's convention: the base lr stays in the group, so a second schedule on the same optimizer
+        # (or one built after load_state_dict) starts from it and not from a scheduled value
+        self.base_lrs = [float(g.setdefault("initial_lr", g["lr"])) for g in optimizer.param_groups]
+        self.last_step = 0
+        self._write()
+
+    def lr_at(self, k, base):
+        """The closed form above for update k and a group's base lr."""
+        W, T = self.warmup_steps, self.total_steps
+        if k < W:
+            return self.warmup_init_lr + (base - self.warmup_init_lr) * k / W
+        if k >= T:
+            return self.min_lr
+        return self.min_lr + 0.5 * (base - self.min_lr) * (1.0 + math.cos(math.pi * (k - W) / max(1, T - W)))
+
+    def _write(self):
+        for g, base in zip(self.optimizer.param_groups, self.base_lrs):
+            g["lr"] = self.lr_at(self.last_step, base)
+
+    def get_last_lr(self):
+        return [g["lr"] for g in self.optimizer.param_groups]
+
+    def step(self):
+        self.last_step += 1
+        self._write()
+
+    def state_dict(self):
+        return {k: v for k, v in self.__dict__.items() if k != "optimizer"}
+
+    def load_state_dict(self, sd):
+        if len(sd["base_lrs"]) != len(self.optimizer.param_groups):
+            raise ValueError(f"WarmupCosineLR.load_state_dict: {len(sd['base_lrs'])} groups saved, the optimizer has "
+                             f"{len(self.optimizer.param_groups)}")
+        self.__dict__.update(sd)
+        self.base_lrs = list(sd["base_lrs"])
+        self._write()

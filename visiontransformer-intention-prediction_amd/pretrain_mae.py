@@ -5,7 +5,10 @@ through dataset.FrameBatchLoader) and discards the labels: ``--stream lidar`` tr
 raster, ``--stream map`` on the map raster. The optimiser is FusedAdamW; its update launch reads the
 loss's device finite flag (and, with ``--clip-grad-norm``, the clip coefficient of
 ``FusedAdamW.grad_norm``), so a step makes no host sync: the per-step losses stay on the device and are
-read once per epoch for the log line.
+read once per epoch for the log line. ``--sched cosine --warmup-epochs E --min-lr X`` is the MAE recipe's
+schedule (optim.WarmupCosineLR, stepped per update; default: constant lr) and ``--no-decay-1d`` its weight
+decay rule (none on norm scales, biases, ``pos_embed``, ``cls_token`` and ``mask_token``; the two groups
+update in one fused launch). Layer-wise lr decay is a fine-tuning device and is not offered here.
 
 Writes ``mae_<stream>.pth`` (the whole model, its config and the optimizer state, for resuming) and
 ``mae_<stream>_encoder.pth`` (the encoder alone, timm keys: what ``train_vit.py --pretrained-lidar`` /
@@ -24,7 +27,7 @@ import torch
 
 from constants import GRID_HEIGHT_PX, GRID_WIDTH_PX, LIDAR_SWEEPS, LIDAR_TOTAL_CHANNELS, MAP_CHANNELS
 from mae import create_mae
-from optim import FusedAdamW
+from optim import FusedAdamW, WarmupCosineLR, layer_decay_param_groups
 from synthetic import SyntheticBEVLoader
 from train_vit import TRAIN_DATA_DIR
 from vit import VIT_ARCH
@@ -53,6 +56,12 @@ def parse_args(argv=None):
     ap.add_argument("--decoder-depth", type=int, default=4)
     ap.add_argument("--lr", type=float, default=1.5e-4)
     ap.add_argument("--weight-decay", type=float, default=0.05)
+    ap.add_argument("--no-decay-1d", action="store_true",
+                    help="no weight decay on 1-D parameters, biases, pos_embed, cls_token and mask_token")
+    ap.add_argument("--sched", choices=["constant", "cosine"], default="constant",
+                    help="cosine: linear warmup then cosine decay to --min-lr over --epochs, stepped every update")
+    ap.add_argument("--warmup-epochs", type=float, default=0.0, metavar="E", help="with --sched cosine")
+    ap.add_argument("--min-lr", type=float, default=0.0, metavar="X", help="with --sched cosine")
     ap.add_argument("--clip-grad-norm", type=float, default=None, metavar="X",
                     help="clip the global gradient L2 norm to X on the device (FusedAdamW.grad_norm, no host sync)")
     ap.add_argument("--augment", action="store_true", help="training-time augment_bev on every batch, on the GPU")
@@ -64,6 +73,11 @@ def parse_args(argv=None):
     args = ap.parse_args(argv)
     if args.decoder_dim <= 0 or args.decoder_dim % 64 != 0:
         ap.error(f"--decoder-dim {args.decoder_dim}: a positive multiple of 64 (the attention head dim)")
+    if args.sched == "cosine":
+        if args.epochs <= 0:
+            ap.error("--sched cosine: the schedule spans --epochs x batches per epoch updates; --epochs must be > 0")
+        if not 0.0 <= args.warmup_epochs <= args.epochs:
+            ap.error(f"--warmup-epochs {args.warmup_epochs:g}: must lie in [0, --epochs]")
     return args
 
 
@@ -101,7 +115,19 @@ def run(args):
         from dataset import ArgoverseIntentNetDataset, FrameBatchLoader
         data = ArgoverseIntentNetDataset(args.data_dir, num_sweeps=args.num_sweeps, is_train=True, device=device)
         loader = FrameBatchLoader(data, args.batch, shuffle=True, rank=0, world=1, augment=args.augment, device=device)
-    opt = FusedAdamW(model.parameters(), lr=args.lr, betas=(0.9, 0.95), weight_decay=args.weight_decay)
+    if args.no_decay_1d:
+        groups = layer_decay_param_groups(model, 1.0, args.weight_decay, no_decay_1d=True)
+        print("Weight decay: " + ", ".join(f"{g['weight_decay']:g} on {len(g['params'])} tensors" for g in groups))
+        opt = FusedAdamW(groups, lr=args.lr, betas=(0.9, 0.95), weight_decay=args.weight_decay, fuse_groups=True)
+    else:
+        opt = FusedAdamW(model.parameters(), lr=args.lr, betas=(0.9, 0.95), weight_decay=args.weight_decay)
+    sched = None
+    if args.sched == "cosine":
+        total = args.epochs * len(loader)
+        if total <= 0:
+            raise SystemExit(f"--sched cosine: no updates to schedule ({args.epochs} epoch(s) x {len(loader)} batch(es))")
+        sched = WarmupCosineLR(opt, int(round(args.warmup_epochs * len(loader))), total, min_lr=args.min_lr)
+        print(f"LR schedule: {sched.warmup_steps} warmup + cosine over {sched.total_steps} updates, min lr {args.min_lr:g}")
     model.train()
     losses, last = [], None
     for epoch in range(args.epochs):
@@ -119,6 +145,8 @@ def run(args):
                 opt.step(finite=gn.finite, grad_scale=gn.coef)
             else:
                 opt.step(finite=fin)
+            if sched is not None:
+                sched.step()
             step_loss.append(loss.detach())
         if not step_loss:
             print(f"Epoch {epoch + 1}: no batches")
@@ -129,13 +157,16 @@ def run(args):
         ok = [v for v in vals if v == v and abs(v) != float("inf")]
         mean = sum(ok) / len(ok) if ok else float("nan")
         print(f"Epoch {epoch + 1}: loss mean {mean:.6f} (first {vals[0]:.6f}, last {vals[-1]:.6f}), "
-              f"{len(vals) - len(ok)} non-finite step(s) skipped  [{len(vals) * args.batch / dt:.1f} samples/s]")
+              f"{len(vals) - len(ok)} non-finite step(s) skipped"
+              + (f", LR {opt.param_groups[0]['lr']:.3e}" if sched is not None else "")
+              + f"  [{len(vals) * args.batch / dt:.1f} samples/s]")
     files = []
     if not args.no_save:
         save_dir = Path(args.save_dir)
         save_dir.mkdir(parents=True, exist_ok=True)
         full, enc = save_dir / f"mae_{args.stream}.pth", save_dir / f"mae_{args.stream}_encoder.pth"
         torch.save({"epoch": args.epochs, "model_state_dict": model.state_dict(), "optimizer_state_dict": opt.state_dict(),
+                    **({"lr_schedule_state_dict": sched.state_dict()} if sched is not None else {}),
                     "mae_cfg": dict(model.config(), arch=args.arch, stream=args.stream, img_size=(H, W),
                                     in_chans=STREAMS[args.stream][1])}, full)
         model.save_encoder(enc)

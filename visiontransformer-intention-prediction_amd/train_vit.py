@@ -27,6 +27,12 @@ same per-batch NaN skips and the same checkpoint dict ({'epoch', 'model_state_di
   adapted to the stream's channels); the saved 'backbone_cfg' keeps ``pretrained_*: False``, so the
   checkpoint stays self-contained. ``--init-from CKPT`` starts from the weights of one of this script's
   checkpoints, trained at the same or another grid (model_vit.load_state_dict_regrid);
+* ``--layer-decay D`` / ``--no-decay-1d`` build the fine-tuning parameter groups of
+  optim.layer_decay_param_groups (lr scaled by D per ViT layer below the top; no weight decay on 1-D
+  parameters, biases, ``pos_embed`` and ``cls_token``) and update them all in ONE launch
+  (``FusedAdamW(fuse_groups=True)``); ``--sched cosine`` replaces ReduceLROnPlateau by optim.WarmupCosineLR,
+  stepped per update (``--warmup-epochs``, ``--min-lr``), and the checkpoint gains 'lr_schedule_state_dict';
+  ``--lr`` / ``--weight-decay`` set the base values. All off by default: one group, plateau schedule;
 * the reference's import-time defects (train_vit.py:34-35 undefined LIDAR_TOTAL_CHANNELS /
   MAP_CHANNELS, :131 ``verbose``) are fixed without changing any value.
 """
@@ -43,7 +49,7 @@ from constants import (ANCHOR_CONFIGS_PAPER, DOMINANT_CLASSES_FOR_DOWNSAMPLING, 
 from ddp import all_reduce_sum, any_rank, init_distributed
 from loss import DetectionIntentionLoss
 from model_vit import BasicBlock, IntentNetViT
-from optim import FusedAdamW, ModelEMA
+from optim import FusedAdamW, ModelEMA, WarmupCosineLR, group_summary, layer_decay_param_groups
 from synthetic import SyntheticBEVLoader
 from trainer import Trainer
 from utils import generate_anchors
@@ -129,7 +135,57 @@ def parse_args(argv=None):
     ap.add_argument("--init-from", type=str, default=None, metavar="CKPT",
                     help="start from the 'model_state_dict' of one of this script's checkpoints, trained at the "
                          "same or another --grid (pos_embed resampled); its optimizer state is not taken")
-    return ap.parse_args(argv)
+    ap.add_argument("--lr", type=float, default=LEARNING_RATE, metavar="X", help="base learning rate")
+    ap.add_argument("--weight-decay", type=float, default=WEIGHT_DECAY, metavar="X")
+    ap.add_argument("--layer-decay", type=float, default=None, metavar="D",
+                    help="layer-wise lr decay in (0, 1]: a ViT stream's block i trains at lr * D ** (depth - i), its "
+                         "patch/pos/cls embeddings at lr * D ** (depth + 1); neck, heads (and all of the CNN) at lr")
+    ap.add_argument("--no-decay-1d", action="store_true",
+                    help="no weight decay on 1-D parameters (norm scales), biases, pos_embed and cls_token")
+    ap.add_argument("--sched", choices=["plateau", "cosine"], default="plateau",
+                    help="plateau: ReduceLROnPlateau on the epoch loss; cosine: linear warmup then cosine decay to "
+                         "--min-lr over --epochs, stepped every update")
+    ap.add_argument("--warmup-epochs", type=float, default=0.0, metavar="E", help="with --sched cosine")
+    ap.add_argument("--min-lr", type=float, default=0.0, metavar="X", help="with --sched cosine")
+    args = ap.parse_args(argv)
+    if args.layer_decay is not None and not 0.0 < args.layer_decay <= 1.0:
+        ap.error(f"--layer-decay {args.layer_decay}: must be in (0, 1]")
+    if args.sched == "cosine":
+        if args.epochs <= 0:
+            ap.error("--sched cosine: the schedule spans --epochs x batches per epoch updates; --epochs must be > 0")
+        if not 0.0 <= args.warmup_epochs <= args.epochs:
+            ap.error(f"--warmup-epochs {args.warmup_epochs:g}: must lie in [0, --epochs]")
+    return args
+
+
+def param_groups_requested(args):
+    """Whether the flags ask for the fine-tuning groups (else: one group, as the reference builds it)."""
+    return args.layer_decay is not None or args.no_decay_1d
+
+
+def build_optimizer(model, args, log=print):
+    """FusedAdamW as the flags ask: by default the reference's single group; with --layer-decay /
+    --no-decay-1d the groups of optim.layer_decay_param_groups, fused into one launch."""
+    if not param_groups_requested(args):
+        return FusedAdamW(model.parameters(), lr=args.lr, weight_decay=args.weight_decay)
+    groups = layer_decay_param_groups(model, 1.0 if args.layer_decay is None else args.layer_decay, args.weight_decay,
+                                      no_decay_1d=args.no_decay_1d)
+    log(f"Parameter groups: {len(groups)} (layer decay {args.layer_decay}, no decay on 1-D: {args.no_decay_1d}), "
+        f"one fused AdamW launch")
+    for lid, scale, tensors, elems in group_summary(groups):
+        log(f"  layer {lid:2d}: lr scale {scale:.6f}, {tensors} tensors, {elems} elements")
+    return FusedAdamW(groups, lr=args.lr, weight_decay=args.weight_decay, fuse_groups=True)
+
+
+def build_schedule(optimizer, args, steps_per_epoch):
+    """WarmupCosineLR over --epochs x steps_per_epoch updates for --sched cosine, else None."""
+    if args.sched != "cosine":
+        return None
+    total = args.epochs * int(steps_per_epoch or 0)
+    if total <= 0:
+        raise SystemExit(f"--sched cosine: no updates to schedule ({args.epochs} epoch(s) x {steps_per_epoch} batch(es) "
+                         f"per epoch); the schedule needs the total from --epochs and the loader's length")
+    return WarmupCosineLR(optimizer, int(round(args.warmup_epochs * steps_per_epoch)), total, min_lr=args.min_lr)
 
 
 def _grid_str(g):
@@ -205,7 +261,7 @@ def main(argv=None, variant="vit"):
     log(f"Training data: {'synthetic' if args.synthetic else args.data_dir}")
     log(f"BEV Image Size for {tag}: {(H, W)}")
     log(f"Using Rotated IoU: {USE_ROTATED_IOU}")
-    log(f"Batch Size: {args.batch}/GPU (global {args.batch * world}), Num Epochs: {args.epochs}, LR: {LEARNING_RATE}")
+    log(f"Batch Size: {args.batch}/GPU (global {args.batch * world}), Num Epochs: {args.epochs}, LR: {args.lr}")
     log(f"Feature Map Stride ({tag}): {stride}")
     log(f"Apply Intention Downsampling: {APPLY_INTENTION_DOWNSAMPLING}")
     log(f"Compute dtype: {args.dtype}")
@@ -241,8 +297,16 @@ def main(argv=None, variant="vit"):
                                      apply_intention_downsampling=APPLY_INTENTION_DOWNSAMPLING,
                                      dominant_intentions=DOMINANT_CLASSES_FOR_DOWNSAMPLING,
                                      intention_downsample_ratio=INTENTION_DOWNSAMPLE_RATIO).to(device)
-    optimizer = FusedAdamW(model.parameters(), lr=LEARNING_RATE, weight_decay=WEIGHT_DECAY)
-    scheduler = torch.optim.lr_scheduler.ReduceLROnPlateau(optimizer, mode='min', factor=0.1, patience=3)
+    optimizer = build_optimizer(model, args, log)
+    # every rank's loader has the same length in lockstep mode or a shorter one ends the epoch for all:
+    # the schedule then simply reaches fewer updates than it spans
+    lr_sched = build_schedule(optimizer, args, len(loader))
+    scheduler = None
+    if lr_sched is None:
+        scheduler = torch.optim.lr_scheduler.ReduceLROnPlateau(optimizer, mode='min', factor=0.1, patience=3)
+    else:
+        log(f"LR schedule: {lr_sched.warmup_steps} warmup + cosine over {lr_sched.total_steps} updates, "
+            f"min lr {args.min_lr:g}")
     anchors = generate_anchors(H, W, stride, ANCHOR_CONFIGS_PAPER, device=device)
     log(f"Anchors generated (stride {stride}), shape: {tuple(anchors.shape)}")
     ema = None
@@ -260,6 +324,8 @@ def main(argv=None, variant="vit"):
         t0 = time.perf_counter()
         for batch_idx, batch in enumerate(_in_lockstep(loader, device) if not args.synthetic else loader):
             d = trainer.step(batch)
+            if lr_sched is not None:
+                lr_sched.step()  # per batch, skipped ones included: the same index on every rank
             if d is None:
                 log(f"Warning: NaN detected at batch {batch_idx + 1}. Skipping batch.")
                 continue
@@ -274,12 +340,13 @@ def main(argv=None, variant="vit"):
         if n_ok > 0:
             avg = (acc / n_ok).tolist()
             log(f"Epoch {epoch + 1} Summary: Avg Loss: {avg[0]:.4f} (Cls: {avg[1]:.4f}, Box: {avg[2]:.4f}, "
-                f"Intent: {avg[3]:.4f}) LR: {optimizer.param_groups[0]['lr']:.1e}  "
+                f"Intent: {avg[3]:.4f}) LR: {optimizer.param_groups[0]['lr']:{'.1e' if lr_sched is None else '.3e'}}  "
                 f"[{n_ok * args.batch / dt:.1f} samples/s]")
             if args.clip_grad_norm is not None:
                 log(grad_clip_line(trainer.grad_stats(), args.clip_grad_norm))
                 trainer.reset_grad_stats()
-            scheduler.step(avg[0])
+            if scheduler is not None:
+                scheduler.step(avg[0])
         else:
             log(f"Epoch {epoch + 1} Warning: No batches processed successfully.")
     log(f"\n--- {tag} Training Finished ---")
@@ -290,6 +357,8 @@ def main(argv=None, variant="vit"):
         path = save_dir / f"{variant}_model.pth"
         ckpt = {'epoch': args.epochs, 'model_state_dict': model.state_dict(),
                 'optimizer_state_dict': optimizer.state_dict(), 'backbone_cfg': cfg}
+        if lr_sched is not None:
+            ckpt['lr_schedule_state_dict'] = lr_sched.state_dict()
         if ema is not None:
             ckpt.update(ema_state_dict=ema.state_dict(model), ema_decay=ema.decay, ema_warmup=ema.warmup)
         torch.save(ckpt, path)
