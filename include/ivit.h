@@ -580,6 +580,62 @@ int ivit_eval_post_rotated(const float* cls, const float* box_rel, const float* 
                            long NA, long K, float conf_thr, double iou_thr, float* out_scores, float* out_boxes,
                            long* out_intent, long* out_count, void* work, long work_bytes, void* stream);
 
+/* Weighted box fusion (box voting) behind the NMS above, and flip test-time augmentation for the
+ * eval post-processing. The reference has neither. Candidates of one sample are rows (box xywha
+ * f32, score f32, intention int32, view in {0, 1}). The sort, the suppression mask (axis or
+ * rotated test) and the greedy walk are those of ivit_nms_batched / ivit_nms_rotated_batched,
+ * unchanged; the kept rows are the leaders.
+ *   Ownership: a suppressed row q belongs to the first leader p in score order whose mask bit
+ *     (p, q) is set, the box that removed it in the walk. Leaders own themselves.
+ *   Alignment (f64): d = a_q - a_p, k = the integer nearest d / (pi/2), delta = d - k * pi/2,
+ *     (w~, l~) = (l_q, w_q) if k is odd, else (w_q, l_q): (w, l, a) = (l, w, a + pi/2) = (w, l, a + pi).
+ *   fuse = 1: with S the sum of the member scores, x = sum(s_q x_q) / S, y, w~, l~ likewise,
+ *     a = a_p + sum(s_q delta_q) / S wrapped into (-pi, pi], all in f64 and rounded once to f32
+ *     (a fixed summation order: bitwise repeatable, independent of the other samples of the
+ *     launch; a cluster whose S is not positive keeps its leader's box); the intention is the
+ *     argmax over the K classes of sum(s_q [intention_q = c]), the lowest class on a tie; the
+ *     score (f32) is m_0 with one view and (m_0 + m_1) * 0.5f with two, m_v the largest member
+ *     score of view v or 0 without one. Fused scores are not thresholded again. Output rows are
+ *     in stable descending order of the fused score, ties in leader order.
+ *   fuse = 0: box, score and intention are the leader's own, in keep order (plain NMS over the
+ *     union of the views).
+ * ivit_nms_fuse_batched: segments as ivit_nms_batched (seg, mask_off, max_n, mask_words);
+ * intentions [total] int32 in 0..K-1 (K <= 32), views [total] int32 or null (all view 0; ignored
+ * with n_views = 1). Sample s's rows go to seg[s] .. seg[s] + count[s] - 1 of out_leader (int64,
+ * the leader's LOCAL row), out_boxes [total, 5], out_scores, out_intent (int64) and out_members
+ * (int32 cluster sizes, the leader included; may be null).
+ * work >= ivit_nms_fuse_batched_workspace(n_samples, total, mask_words, rotated): the NMS
+ * workspace plus 28 B per row (keep list, rank, owner and one fused row's score / intention /
+ * member count; the fused boxes reuse the sorted-corner rows, dead after the mask).             */
+long ivit_nms_fuse_batched_workspace(long n_samples, long total, long mask_words, int rotated);
+int ivit_nms_fuse_batched(const float* boxes_xywha, const float* scores, const int* intentions, const int* views,
+                          const long* seg, const long* mask_off, long n_samples, long total, long max_n,
+                          long mask_words, long K, long n_views, int fuse, int rotated, double iou_thr,
+                          long* out_leader, float* out_boxes, float* out_scores, long* out_intent, int* out_members,
+                          long* count, void* work, long work_bytes, void* stream);
+
+/* ivit_eval_post over V in {1, 2} views of the same B scenes, view 1 the forward of the mirrored
+ * rasters (the training flip: ivit_bev_augment's flip). cls [V, B, NA], box_rel [V, B, NA, 6],
+ * intent [V, B, NA, K], one anchor set [NA, 5]. Per sample: sigmoid >= conf_thr per view in anchor
+ * order, decode, the row's argmax intention; view 1 un-mirrored (y and the yaw negated, both
+ * exactly; the intention through the HOST table flip_intent[K], null = identity); view-0 rows
+ * first, then view-1 rows; then the shared sort / mask / walk and the fusion above. Capacity
+ * C = V * NA rows per sample, C <= 131072. Outputs as ivit_eval_post with row stride C:
+ * out_scores [B, C], out_boxes [B, C, 5], out_intent [B, C] (int64), out_members [B, C] (int32,
+ * may be null), out_count [B]; nothing is read back. V = 1, fuse = 0 gives ivit_eval_post's rows
+ * bit for bit.
+ * work >= ivit_eval_post_tta_workspace(B, V, NA, rotated): ivit_eval_post's layout for B samples
+ * of C anchors plus 24 B per row + 4 B per sample. The mask grows with C^2, so a caller that must
+ * stay within the workspace it already reserves for ivit_eval_post(B, NA) (rotated:
+ * ivit_eval_post_rotated) runs the batch in chunks of Bc samples, Bc the largest value with
+ * ivit_eval_post_tta_workspace(Bc, V, NA, rotated) <= ivit_eval_post[_rotated]_workspace(B, NA),
+ * at least 1: about B / 4 samples per launch set for two views (utils.tta_chunk).              */
+long ivit_eval_post_tta_workspace(long B, long V, long NA, int rotated);
+int ivit_eval_post_tta(const float* cls, const float* box_rel, const float* intent, const float* anchors, long V,
+                       long B, long NA, long K, const int* flip_intent, float conf_thr, double iou_thr, int rotated,
+                       int fuse, float* out_scores, float* out_boxes, long* out_intent, int* out_members,
+                       long* out_count, void* work, long work_bytes, void* stream);
+
 /* ---- BEV augmentation passes ----------------------------------------
  * Replaces the raster side of utils.augment_bev (utils.py:500-517): random_flip_bev's np.flip
  * (:399-401), random_rotate_bev's per-channel cv2.warpAffine (:425-438), random_scale_bev's

@@ -60,6 +60,8 @@ DETECTION_IOU_THRESHOLDS = [0.5, 0.6, 0.7, 0.8, 0.9]
 IOU_THRESHOLD_FOR_INTENTION_MATCH = 0.5
 EVAL_USE_ROTATED_IOU = False
 EVAL_USE_ROTATED_NMS = False  # eval_vit.py --rotated-nms: suppress on the rotated IoU of the decoded boxes
+EVAL_TTA_FLIP = False  # eval_vit.py --tta-flip: a second forward on the mirrored rasters, merged before the NMS
+EVAL_FUSE_BOXES = False  # eval_vit.py --fuse-boxes: kept boxes become the weighted fusion of what they suppressed
 
 # train_vit.py / train_cnn.py --clip-grad-norm: global gradient L2-norm bound (None: no clipping, the reference's loop)
 GRAD_CLIP_NORM = None

@@ -1110,3 +1110,488 @@ extern "C" int ivit_eval_post_rotated(const float* cls, const float* box_rel, co
                         out_scores, out_boxes, out_intent, out_count, work, work_bytes, stream);
 }
 
+
+// ---- weighted box fusion behind the NMS stages (ivit_nms_fuse_batched, ivit_eval_post_tta) -------
+// The sort, the suppression mask and the greedy walk are the shared ones, unchanged. When the walk
+// ends the full upper-triangular mask is still in memory: row p of a kept box (a leader) names
+// every later sorted box it overlaps. A suppressed box q was removed by the FIRST leader in score
+// order whose row has bit q (the walk ORs the rows of the kept boxes in that order), so
+//   fuse_rank_kernel   rank[] = the inverse of order[] (a leader's sorted position), owner[] = none;
+//   fuse_owner_kernel  one wave per leader j over its mask row: atomicMin(owner[q], j) for every
+//                      set bit (an integer minimum: the arrival order cannot change it);
+//   fuse_cluster_kernel one wave per leader j over the same row, keeping the bits q whose owner is
+//                      j: the score-weighted f64 sums of the members aligned to the leader, the
+//                      intention vote, the per-view score maxima, the member count. Lane l adds the
+//                      members of words first + l, first + l + 64, ... in ascending bit order
+//                      (lane 0 starts with the leader itself), then the 64 partial sums are added in
+//                      a fixed xor butterfly (a + b = b + a bitwise, so every lane holds the same
+//                      sum): the order is a function of the sample's own rows alone;
+//   fuse_emit_kernel   one workgroup per sample: the stable descending sort of the fused scores
+//                      (two views with fusion only; otherwise the keep order is that order
+//                      already) and the packed output rows.
+// Two leaders never share a bit (a kept box is not overlapped by an earlier kept box), so a
+// leader's own entry is written by its own wave alone.
+namespace {
+struct FuseWs {
+  const float* box;    // candidate rows, unsorted xywha
+  const float* score;
+  const int* intent;
+  const int* views;    // per row, or null
+  const int* split;    // [S] rows of view 0 (the rest are view 1), or null; views wins
+  const int* order;
+  const long* keep;
+  const long* count;
+  const unsigned long long* mask;
+  int* rank;           // [rows] sorted position of local row r
+  int* owner;          // [rows] by sorted position: the owning leader's place in the keep list
+  float* tbox;         // [rows*5] per leader j (the corner rows' region: dead after the mask)
+  float* tscore;       // [rows]
+  int* tint;           // [rows]
+  int* tmem;           // [rows]
+  unsigned *k0, *k1;   // the sort scratch, dead after the first sort
+  int *v0, *v1;
+  int K, n_views, fuse;
+};
+constexpr int FUSE_NONE = 0x7fffffff;
+constexpr int FUSE_MAXK = 32;
+constexpr double FUSE_HALF_PI = 1.5707963267948966;
+constexpr double FUSE_PI = 3.141592653589793;
+
+IVIT_DEV int fuse_view(const FuseWs& f, int sm, long o, int r) {
+  if (f.n_views < 2) return 0;
+  if (f.views) return f.views[o + r] != 0;
+  return f.split ? r >= f.split[sm] : 0;
+}
+
+// grid (ceil(max n / 256), samples)
+__global__ __launch_bounds__(256) void fuse_rank_kernel(FuseWs f, SegView sv) {
+  const int sm = blockIdx.y;
+  const long o = sv.lo(sm), n = sv.n(sm);
+  const long p = (long)blockIdx.x * 256 + threadIdx.x;
+  if (p >= n) return;
+  f.rank[o + f.order[o + p]] = (int)p;
+  f.owner[o + p] = FUSE_NONE;
+}
+
+// grid (x, samples), 4 waves per workgroup, leaders strided over the sample's waves
+__global__ __launch_bounds__(256) void fuse_owner_kernel(FuseWs f, SegView sv) {
+  const int sm = blockIdx.y, lane = threadIdx.x & 63;
+  const long o = sv.lo(sm), n = sv.n(sm);
+  const int nw = (int)((n + 63) / 64);
+  const long cnt = min(f.count[sm], n);
+  const unsigned long long* mask = f.mask + sv.mo(sm);
+  for (long j = (long)blockIdx.x * 4 + (threadIdx.x >> 6); j < cnt; j += (long)gridDim.x * 4) {
+    const int p = f.rank[o + f.keep[o + j]];
+    if (lane == 0) atomicMin(&f.owner[o + p], (int)j);
+    const unsigned long long* row = mask + (long)p * nw;
+    for (int w = (p >> 6) + lane; w < nw; w += 64) {
+      unsigned long long bits = row[w];
+      while (bits) {
+        const long q = (long)w * 64 + __builtin_ctzll(bits);
+        bits &= bits - 1ull;
+        if (q < n) atomicMin(&f.owner[o + q], (int)j);
+      }
+    }
+  }
+}
+
+IVIT_DEV double wave_sum_f64(double v) {
+#pragma unroll
+  for (int s = 32; s >= 1; s >>= 1) v += __shfl_xor(v, s, 64);
+  return v;
+}
+
+// grid (x, samples), one wave per workgroup, leaders strided over the sample's workgroups
+__global__ __launch_bounds__(64) void fuse_cluster_kernel(FuseWs f, SegView sv) {
+  __shared__ double vote[FUSE_MAXK][64];
+  const int sm = blockIdx.y, lane = threadIdx.x;
+  const long o = sv.lo(sm), n = sv.n(sm);
+  const int nw = (int)((n + 63) / 64);
+  const long cnt = min(f.count[sm], n);
+  const unsigned long long* mask = f.mask + sv.mo(sm);
+  for (long j = blockIdx.x; j < cnt; j += gridDim.x) {
+    const int rp = (int)f.keep[o + j];
+    const int p = f.rank[o + rp];
+    const float* bp = f.box + (o + rp) * 5;
+    const double ap = (double)bp[4];
+    double S = 0.0, sx = 0.0, sy = 0.0, sw = 0.0, sl = 0.0, sd = 0.0;
+    float m0 = -INFINITY, m1 = -INFINITY;
+    int members = 0;
+    if (f.fuse)
+      for (int c = 0; c < f.K; ++c) vote[c][lane] = 0.0;
+    auto member = [&](int q) {
+      const int r = f.order[o + q];
+      ++members;
+      if (!f.fuse) return;
+      const float* b = f.box + (o + r) * 5;
+      const float sc = f.score[o + r];
+      const double s = (double)sc;
+      const double d = (double)b[4] - ap;
+      const double k = rint(d / FUSE_HALF_PI);
+      const double delta = d - k * FUSE_HALF_PI;
+      const bool odd = ((long long)k) & 1;
+      S += s;
+      sx += s * (double)b[0];
+      sy += s * (double)b[1];
+      sw += s * (double)(odd ? b[3] : b[2]);
+      sl += s * (double)(odd ? b[2] : b[3]);
+      sd += s * delta;
+      const int c = f.intent[o + r];
+      if (c >= 0 && c < f.K) vote[c][lane] += s;
+      if (fuse_view(f, sm, o, r)) m1 = fmaxf(m1, sc);
+      else m0 = fmaxf(m0, sc);
+    };
+    if (lane == 0) member(p);
+    const unsigned long long* row = mask + (long)p * nw;
+    for (int w = (p >> 6) + lane; w < nw; w += 64) {
+      unsigned long long bits = row[w];
+      while (bits) {
+        const long q = (long)w * 64 + __builtin_ctzll(bits);
+        bits &= bits - 1ull;
+        if (q < n && f.owner[o + q] == (int)j) member((int)q);
+      }
+    }
+#pragma unroll
+    for (int s = 32; s >= 1; s >>= 1) members += __shfl_xor(members, s, 64);
+    float ob[5] = {bp[0], bp[1], bp[2], bp[3], bp[4]};
+    float osc = f.score[o + rp];
+    int oint = f.intent[o + rp];
+    if (f.fuse) {
+      S = wave_sum_f64(S);
+      sx = wave_sum_f64(sx);
+      sy = wave_sum_f64(sy);
+      sw = wave_sum_f64(sw);
+      sl = wave_sum_f64(sl);
+      sd = wave_sum_f64(sd);
+#pragma unroll
+      for (int s = 32; s >= 1; s >>= 1) {
+        m0 = fmaxf(m0, __shfl_xor(m0, s, 64));
+        m1 = fmaxf(m1, __shfl_xor(m1, s, 64));
+      }
+      double best = 0.0;
+      int bc = 0;
+      for (int c = 0; c < f.K; ++c) {
+        const double v = wave_sum_f64(vote[c][lane]);
+        if (c == 0 || v > best) {  // the lowest class wins a tie
+          best = v;
+          bc = c;
+        }
+      }
+      oint = bc;
+      if (S > 0.0) {  // a cluster without positive weight keeps the leader's box
+        double a = ap + sd / S;
+        if (a > FUSE_PI) a -= 2.0 * FUSE_PI;
+        else if (a <= -FUSE_PI) a += 2.0 * FUSE_PI;
+        ob[0] = (float)(sx / S);
+        ob[1] = (float)(sy / S);
+        ob[2] = (float)(sw / S);
+        ob[3] = (float)(sl / S);
+        ob[4] = (float)a;
+      }
+      const float z0 = m0 == -INFINITY ? 0.f : m0, z1 = m1 == -INFINITY ? 0.f : m1;
+      osc = f.n_views == 2 ? (z0 + z1) * 0.5f : z0;
+    }
+    if (lane == 0) {
+#pragma unroll
+      for (int e = 0; e < 5; ++e) f.tbox[(o + j) * 5 + e] = ob[e];
+      f.tscore[o + j] = osc;
+      f.tint[o + j] = oint;
+      f.tmem[o + j] = members;
+    }
+    __syncthreads();  // one wave: the next leader clears vote[] after every lane has read it
+  }
+}
+
+// grid (samples). direct: no cluster stage ran (fuse = 0 and no member counts asked for); the rows
+// are the leaders' own, read from the candidates.
+__global__ __launch_bounds__(PS_T) void fuse_emit_kernel(FuseWs f, SegView sv, int direct, long* __restrict__ out_leader,
+                                                         float* __restrict__ out_box, float* __restrict__ out_score,
+                                                         long* __restrict__ out_int, int* __restrict__ out_mem) {
+  __shared__ unsigned hist[PS_D * PS_T];
+  __shared__ unsigned wsum[20];
+  __shared__ int skip;
+  const int sm = blockIdx.x;
+  const long o = sv.lo(sm);
+  const int cnt = (int)min(f.count[sm], sv.n(sm));
+  const int* perm = nullptr;
+  if (f.fuse && f.n_views == 2 && !direct) {
+    for (int j = threadIdx.x; j < cnt; j += PS_T) {
+      f.k0[o + j] = desc_key(f.tscore[o + j]);
+      f.v0[o + j] = j;
+    }
+    __syncthreads();
+    const int r = block_radix_sort(f.k0 + o, f.v0 + o, f.k1 + o, f.v1 + o, cnt, hist, wsum, &skip);
+    perm = (r ? f.v1 : f.v0) + o;
+  }
+  for (int i = threadIdx.x; i < cnt; i += PS_T) {
+    const int j = perm ? perm[i] : i;
+    const long lr = f.keep[o + j];
+    const float* b = direct ? f.box + (o + lr) * 5 : f.tbox + (o + j) * 5;
+    if (out_leader) out_leader[o + i] = lr;
+#pragma unroll
+    for (int e = 0; e < 5; ++e) out_box[(o + i) * 5 + e] = b[e];
+    out_score[o + i] = direct ? f.score[o + lr] : f.tscore[o + j];
+    out_int[o + i] = direct ? f.intent[o + lr] : f.tint[o + j];
+    if (out_mem) out_mem[o + i] = direct ? 1 : f.tmem[o + j];
+  }
+}
+
+// The stages after the walk. keep / count: the walk's outputs.
+void fuse_stages(const FuseWs& f, const SegView& sv, long samples, long max_n, long* out_leader, float* out_box,
+                 float* out_score, long* out_int, int* out_mem, hipStream_t st) {
+  const int direct = !f.fuse && !out_mem;
+  if (!direct) {
+    hipLaunchKernelGGL(fuse_rank_kernel, dim3(ivit_cdiv(max_n, 256), samples), dim3(256), 0, st, f, sv);
+    hipLaunchKernelGGL(fuse_owner_kernel, dim3((int)min((long)64, (max_n + 3) / 4), samples), dim3(256), 0, st, f, sv);
+    hipLaunchKernelGGL(fuse_cluster_kernel, dim3((int)min((long)256, max_n), samples), dim3(64), 0, st, f, sv);
+  }
+  hipLaunchKernelGGL(fuse_emit_kernel, dim3(samples), dim3(PS_T), 0, st, f, sv, direct, out_leader, out_box,
+                     out_score, out_int, out_mem);
+}
+
+// The fusion scratch, placed behind the NMS workspace's regions: rank, owner, tscore, tint, tmem,
+// each [rows] and rounded up to 16 bytes.
+constexpr int FUSE_REGIONS = 5;
+long fuse_extra_bytes(long rows) { return FUSE_REGIONS * al16(4 * rows); }
+void fuse_extra(char* p, long rows, FuseWs& f) {
+  const long step = al16(4 * rows);
+  f.rank = (int*)p;
+  f.owner = (int*)(p + step);
+  f.tscore = (float*)(p + 2 * step);
+  f.tint = (int*)(p + 3 * step);
+  f.tmem = (int*)(p + 4 * step);
+}
+
+// ivit_nms_fuse_batched's workspace: BatchWs, then the walk's keep list (8 B per row), then the
+// fusion scratch.
+long fuse_batch_bytes(long n_samples, long total, long mask_words, bool rotated) {
+  if (n_samples <= 0 || total <= 0) return 64;
+  return batch_ws(nullptr, total, mask_words, rotated).bytes + al16(8 * total) + fuse_extra_bytes(total);
+}
+
+// ---- ivit_eval_post_tta: the selection of ivit_eval_post over V views of the same scenes ----------
+struct TtaIn {
+  const float* cls;     // [V, B, NA]
+  const float* rel;     // [V, B, NA, 6]
+  const float* intent;  // [V, B, NA, K]
+  int B, NA, K, V;
+  int flip[FUSE_MAXK];  // view 1: the intention a mirrored scene's class means in the original one
+  int* cint;            // [B * V * NA] candidate intentions
+  int* split;           // [B] rows of view 0
+};
+
+// torch's argmax over K logits: the first maximum; a NaN is the maximum, the first NaN wins
+IVIT_DEV int argmax_first(const float* lg, int K) {
+  int best = 0;
+  float bv = lg[0];
+  for (int e = 1; e < K; ++e) {
+    const float v = lg[e];
+    if (bv == bv && (v > bv || v != v)) {
+      bv = v;
+      best = e;
+    }
+  }
+  return best;
+}
+
+// post_select_kernel for sample blockIdx.x with capacity V * NA rows: view 0's passing anchors in
+// anchor order, then view 1's, un-mirrored (the inverse of the training flip: y and the yaw
+// negated, both exactly; the intention through the table); every row's argmax intention; then the
+// same stable descending sort and corner rows.
+__global__ __launch_bounds__(PS_T) void post_select_tta_kernel(TtaIn in, const float* __restrict__ anchors, float conf,
+                                                               PostWs w) {
+  __shared__ unsigned hist[PS_D * PS_T];
+  __shared__ unsigned wsum[20];
+  __shared__ int skip;
+  const int sm = blockIdx.x, t = threadIdx.x, NA = in.NA;
+  const long base = (long)sm * in.V * NA;
+  const int I = (NA + PS_T - 1) / PS_T;
+  const int a0 = min(t * I, NA), a1 = min(a0 + I, NA);
+  unsigned done = 0;
+  for (int v = 0; v < in.V; ++v) {
+    const long vb = ((long)v * in.B + sm) * NA;
+    const float* c = in.cls + vb;
+    const float* r = in.rel + vb * 6;
+    unsigned np = 0;
+    for (int g0 = a0; g0 < a1; g0 += 8) {
+      float lr[8];
+#pragma unroll
+      for (int e = 0; e < 8; ++e) lr[e] = g0 + e < a1 ? c[g0 + e] : 0.f;
+#pragma unroll
+      for (int e = 0; e < 8; ++e) np += g0 + e < a1 && torch_sigmoid(lr[e]) >= conf;
+    }
+    unsigned p = done + block_excl_scan(np, wsum);
+    const unsigned tot = wsum[16];
+    for (int g0 = a0; g0 < a1; g0 += 8) {
+      float lr[8];
+#pragma unroll
+      for (int e = 0; e < 8; ++e) lr[e] = g0 + e < a1 ? c[g0 + e] : 0.f;
+#pragma unroll
+      for (int e = 0; e < 8; ++e) {
+        const int a = g0 + e;
+        const float s = torch_sigmoid(lr[e]);
+        if (a < a1 && s >= conf) {
+          const long q = base + p;
+          w.anchor[q] = v * NA + a;
+          w.score[q] = s;
+          w.k0[q] = desc_key(s);
+          w.v0[q] = (int)p;
+          float o[5];
+          decode_one(r + (long)a * 6, anchors + (long)a * 5, o);
+          if (v) {
+            o[1] = -o[1];
+            o[4] = -o[4];
+          }
+#pragma unroll
+          for (int k = 0; k < 5; ++k) w.box[q * 5 + k] = o[k];
+          const int cl = argmax_first(in.intent + (vb + a) * in.K, in.K);
+          in.cint[q] = v ? in.flip[cl] : cl;
+          ++p;
+        }
+      }
+    }
+    if (t == 0 && v == 0) in.split[sm] = (int)tot;
+    done += tot;
+    __syncthreads();  // wsum[16] has been read by every thread before the next view's scan
+  }
+  const int n = (int)done;
+  if (t == 0) w.n[sm] = n;
+  __syncthreads();
+  const int res = block_radix_sort(w.k0 + base, w.v0 + base, w.k1 + base, w.v1 + base, n, hist, wsum, &skip);
+  const int* ord = (res ? w.v1 : w.v0) + base;
+  for (int i = t; i < n; i += PS_T) {
+    const int q = ord[i];
+    w.order[base + i] = q;
+    sorted_corners(w.box + (base + q) * 5, w.sb + (base + i) * 5);
+  }
+}
+
+// ivit_eval_post_tta's workspace: ivit_eval_post's layout at capacity V * NA rows per sample, then
+// the candidate intentions (4 B per row), the view-0 counts (4 B per sample), the fusion scratch.
+long tta_ws_bytes(long B, long V, long NA, bool rotated) {
+  if (B <= 0 || NA <= 0 || V <= 0) return 64;
+  const long R = B * V * NA;
+  return post_layout(B, V * NA, rotated).bytes + al16(4 * R) + al16(4 * B) + fuse_extra_bytes(R);
+}
+}  // namespace
+
+extern "C" long ivit_nms_fuse_batched_workspace(long n_samples, long total, long mask_words, int rotated) {
+  return fuse_batch_bytes(n_samples, total, mask_words, rotated != 0);
+}
+
+extern "C" int ivit_nms_fuse_batched(const float* boxes_xywha, const float* scores, const int* intentions,
+                                     const int* views, const long* seg, const long* mask_off, long n_samples,
+                                     long total, long max_n, long mask_words, long K, long n_views, int fuse,
+                                     int rotated, double iou_thr, long* out_leader, float* out_boxes,
+                                     float* out_scores, long* out_intent, int* out_members, long* count, void* work,
+                                     long work_bytes, void* stream) {
+  const char* name = "ivit_nms_fuse_batched";
+  IVIT_CHECK_ARG(n_views == 1 || n_views == 2, "%s: n_views must be 1 or 2 (got %ld)", name, n_views);
+  IVIT_CHECK_ARG(K >= 1 && K <= FUSE_MAXK, "%s: K must be in 1..%d (got %ld)", name, FUSE_MAXK, K);
+  IVIT_CHECK_ARG(max_n <= 64L * NMS_MAXW, "%s: n=%ld exceeds %d", name, max_n, 64 * NMS_MAXW);
+  IVIT_CHECK_ARG(n_samples >= 0 && n_samples < 65536 && total >= 0 && total < (1L << 31) && max_n >= 0 &&
+                     mask_words >= 0,
+                 "%s: bad sizes (samples %ld, rows %ld)", name, n_samples, total);
+  IVIT_CHECK_ARG(work_bytes >= fuse_batch_bytes(n_samples, total, mask_words, rotated != 0), "%s: workspace too small",
+                 name);
+  IVIT_CHECK_ARG(intentions != nullptr || total == 0, "%s: intentions is null", name);
+  hipStream_t st = ivit_stream(stream);
+  if (n_samples <= 0) return 0;
+  if (max_n <= 0 || total <= 0) {
+    (void)hipMemsetAsync(count, 0, sizeof(long) * n_samples, st);
+    return launch_status(name);
+  }
+  const BatchWs w = batch_ws(work, total, mask_words, rotated != 0);
+  char* tail = (char*)(((uintptr_t)work + 15) & ~(uintptr_t)15) + (w.bytes - 64);
+  long* keep = (long*)tail;
+  const SegView sv{seg, mask_off, nullptr, 0, 0};
+  hipLaunchKernelGGL(nms_sort_b_kernel, dim3(n_samples), dim3(PS_T), 0, st, boxes_xywha, scores, seg, w.k0, w.v0, w.k1,
+                     w.v1, w.order, w.sb);
+  nms_mask_and_scan(boxes_xywha, w.order, w.sb, w.rp, w.rc, w.mask, sv, n_samples, max_n, iou_thr, rotated != 0, keep,
+                    count, st);
+  FuseWs f{};
+  f.box = boxes_xywha;
+  f.score = scores;
+  f.intent = intentions;
+  f.views = n_views == 2 ? views : nullptr;
+  f.order = w.order;
+  f.keep = keep;
+  f.count = count;
+  f.mask = w.mask;
+  f.tbox = w.sb;
+  f.k0 = w.k0;
+  f.k1 = w.k1;
+  f.v0 = w.v0;
+  f.v1 = w.v1;
+  f.K = (int)K;
+  f.n_views = (int)n_views;
+  f.fuse = fuse != 0;
+  fuse_extra(tail + al16(8 * total), total, f);
+  fuse_stages(f, sv, n_samples, max_n, out_leader, out_boxes, out_scores, out_intent, out_members, st);
+  return launch_status(name);
+}
+
+extern "C" long ivit_eval_post_tta_workspace(long B, long V, long NA, int rotated) {
+  return tta_ws_bytes(B, V, NA, rotated != 0);
+}
+
+extern "C" int ivit_eval_post_tta(const float* cls, const float* box_rel, const float* intent, const float* anchors,
+                                  long V, long B, long NA, long K, const int* flip_intent, float conf_thr,
+                                  double iou_thr, int rotated, int fuse, float* out_scores, float* out_boxes,
+                                  long* out_intent, int* out_members, long* out_count, void* work, long work_bytes,
+                                  void* stream) {
+  const char* name = "ivit_eval_post_tta";
+  IVIT_CHECK_ARG(V == 1 || V == 2, "%s: V must be 1 or 2 (got %ld)", name, V);
+  IVIT_CHECK_ARG(K >= 1 && K <= FUSE_MAXK, "%s: K must be in 1..%d (got %ld)", name, FUSE_MAXK, K);
+  IVIT_CHECK_ARG(B >= 0 && B < 65536 && NA >= 0, "%s: bad sizes (B %ld, NA %ld)", name, B, NA);
+  IVIT_CHECK_ARG(V * NA <= 64L * NMS_MAXW, "%s: V*NA=%ld exceeds %d", name, V * NA, 64 * NMS_MAXW);
+  IVIT_CHECK_ARG(B * V * NA < (1L << 31), "%s: too many rows (%ld)", name, B * V * NA);
+  TtaIn in{};
+  for (int k = 0; k < (int)K; ++k) {
+    in.flip[k] = flip_intent ? flip_intent[k] : k;
+    IVIT_CHECK_ARG(in.flip[k] >= 0 && in.flip[k] < K, "%s: flip_intent[%d]=%d outside 0..%ld", name, k, in.flip[k],
+                   K - 1);
+  }
+  IVIT_CHECK_ARG(work_bytes >= tta_ws_bytes(B, V, NA, rotated != 0), "%s: workspace too small", name);
+  hipStream_t st = ivit_stream(stream);
+  if (B == 0) return 0;
+  if (NA == 0) {
+    (void)hipMemsetAsync(out_count, 0, sizeof(long) * B, st);
+    return launch_status(name);
+  }
+  const long C = V * NA, R = B * C;
+  const PostWs w = post_ws(work, B, C, rotated != 0);
+  char* tail = (char*)(((uintptr_t)work + 15) & ~(uintptr_t)15) + (post_layout(B, C, rotated != 0).bytes - 16);
+  in.cls = cls;
+  in.rel = box_rel;
+  in.intent = intent;
+  in.B = (int)B;
+  in.NA = (int)NA;
+  in.K = (int)K;
+  in.V = (int)V;
+  in.cint = (int*)tail;
+  in.split = (int*)(tail + al16(4 * R));
+  const SegView sv{nullptr, nullptr, w.n, C, C * ((C + 63) / 64)};
+  hipLaunchKernelGGL(post_select_tta_kernel, dim3(B), dim3(PS_T), 0, st, in, anchors, conf_thr, w);
+  nms_mask_and_scan(w.box, w.order, w.sb, w.rp, w.rc, w.mask, sv, B, C, iou_thr, rotated != 0, w.keep, out_count, st);
+  FuseWs f{};
+  f.box = w.box;
+  f.score = w.score;
+  f.intent = in.cint;
+  f.split = V == 2 ? in.split : nullptr;
+  f.order = w.order;
+  f.keep = w.keep;
+  f.count = out_count;
+  f.mask = w.mask;
+  f.tbox = w.sb;
+  f.k0 = w.k0;
+  f.k1 = w.k1;
+  f.v0 = w.v0;
+  f.v1 = w.v1;
+  f.K = (int)K;
+  f.n_views = (int)V;
+  f.fuse = fuse != 0;
+  fuse_extra(tail + al16(4 * R) + al16(4 * B), R, f);
+  fuse_stages(f, sv, B, C, nullptr, out_boxes, out_scores, out_intent, out_members, st);
+  return launch_status(name);
+}

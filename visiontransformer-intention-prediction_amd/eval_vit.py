@@ -15,6 +15,11 @@ on the device for the whole batch (utils.postprocess_batch, pipelined by utils.P
 walk runs on the device for all samples in one launch (metrics.match_device, ivit_det_match). The reference's undefined names (eval_vit.py:12-13,39,196,219)
 come from constants.py / utils.py. ``--rotated-nms`` (off by default; the reference's future work)
 makes the NMS suppress on the rotated IoU of the decoded boxes instead of their axis-aligned corners.
+``--tta-flip`` (off by default) runs every batch a second time on the mirrored rasters (the training
+flip) and merges both views' candidates, the second un-mirrored, before the NMS; ``--fuse-boxes``
+(off by default) replaces every kept box by the score-weighted fusion of the candidates it
+suppressed and its intention by their weighted vote (utils.postprocess_batch, ivit_eval_post_tta).
+The two are independent of each other and of ``--rotated-nms``.
 ``--attn-maps DIR`` (the reference's other future-work item, qualitative analysis of the attention)
 writes, per batch, the attention maps of both ViT streams for each sample's ``--attn-top`` best
 detections at ``--attn-blocks`` (AttnDump; IntentNetViT.attention_maps).
@@ -44,13 +49,13 @@ import numpy as np
 import torch
 
 import model_vit
-from constants import (ANCHOR_CONFIGS_PAPER, DETECTION_IOU_THRESHOLDS, EVAL_USE_ROTATED_IOU, EVAL_USE_ROTATED_NMS,
-                       GRID_HEIGHT_PX, GRID_WIDTH_PX, INTENTIONS_MAP_REV, IOU_THRESHOLD_FOR_INTENTION_MATCH,
+from constants import (ANCHOR_CONFIGS_PAPER, DETECTION_IOU_THRESHOLDS, EVAL_FUSE_BOXES, EVAL_TTA_FLIP,
+                       EVAL_USE_ROTATED_IOU, EVAL_USE_ROTATED_NMS, GRID_HEIGHT_PX, GRID_WIDTH_PX, INTENTIONS_MAP_REV, IOU_THRESHOLD_FOR_INTENTION_MATCH,
                        LIDAR_SWEEPS, LIDAR_TOTAL_CHANNELS, MAP_CHANNELS, NUM_INTENTION_CLASSES)
 from metrics import detection_map_device as detection_map, intention_matches_device as intention_matches
 from model_vit import IntentNetViT
 from synthetic import SyntheticBEVLoader
-from utils import PostPipeline, generate_anchors
+from utils import PostPipeline, flip_bev_batch, generate_anchors
 
 VAL_DATA_DIR = "./data/argoverse2/sensor/val"
 MODEL_SAVE_PATH_VIT = "./trained_models_vit/vit_model.pth"
@@ -99,6 +104,12 @@ def parse_args(argv=None):
                     help="rotated IoU for mAP / matching (device kernel; no shapely needed)")
     ap.add_argument("--rotated-nms", action="store_true", default=EVAL_USE_ROTATED_NMS,
                     help="suppress on the rotated IoU of the decoded boxes (independent of --rotated)")
+    ap.add_argument("--tta-flip", action="store_true", default=EVAL_TTA_FLIP,
+                    help="flip test-time augmentation: a second forward on the mirrored rasters, its candidates "
+                         "un-mirrored and merged with the first view's before the NMS")
+    ap.add_argument("--fuse-boxes", action="store_true", default=EVAL_FUSE_BOXES,
+                    help="weighted box fusion: every kept box becomes the score-weighted consensus of the candidates "
+                         "it suppressed, its intention their weighted vote (independent of --tta-flip)")
     ap.add_argument("--attn-maps", type=str, default=None, metavar="DIR",
                     help="write the attention maps of each sample's best detections, one .npz per batch (ViT only)")
     ap.add_argument("--attn-top", type=int, default=8, help="detections per sample (highest score after NMS)")
@@ -153,15 +164,19 @@ class AttnDump:
 
 
 def run_inference(model, loader, anchors, conf=CONFIDENCE_THRESHOLD, nms=NMS_IOU_THRESHOLD, rotated_nms=False,
-                  attn_dump=None):
+                  attn_dump=None, tta_flip=False, fuse_boxes=False):
     """eval_vit.py:136-180: forward + post-processing per batch, in loader order. The
     post-processing of a batch (utils.PostPipeline) runs beside the next batch's forward; results
     are the per-batch postprocess_batch ones, appended in the same order. ``rotated_nms``: the
     NMS suppresses on the rotated IoU (utils.apply_nms(rotated=True)). ``attn_dump`` (AttnDump):
     a batch's inputs are kept until its detections arrive (one batch late), then its attention
-    maps are computed and written; the results are the same with and without it."""
+    maps are computed and written; the results are the same with and without it.
+    ``tta_flip``: every batch is also run mirrored (utils.flip_bev_batch) and both views' candidates
+    go through one NMS; ``fuse_boxes``: the kept boxes are fused with what they suppressed
+    (utils.postprocess_batch). With either, the results gain 'pred_members'."""
     results = []
-    pipe = PostPipeline(anchors, conf, nms, rotated_nms=rotated_nms)
+    tta_kw = {k: True for k, v in (("tta_flip", tta_flip), ("fuse_boxes", fuse_boxes)) if v}
+    pipe = PostPipeline(anchors, conf, nms, rotated_nms=rotated_nms, **tta_kw)
     gts = []
     held = []  # attn_dump: the (lidar, map) rasters of the batches whose detections are still pending
 
@@ -181,7 +196,10 @@ def run_inference(model, loader, anchors, conf=CONFIDENCE_THRESHOLD, nms=NMS_IOU
             gts.append(batch["gt_list"])
             if attn_dump is not None:
                 held.append((lidar, mp))
-            prev = pipe.push(cls, box, it)
+            if tta_flip:
+                prev = pipe.push(cls, box, it, tta_logits=model(*flip_bev_batch(lidar, mp)))
+            else:
+                prev = pipe.push(cls, box, it)
             if prev is not None:
                 emit(prev)
         last = pipe.flush()
@@ -208,6 +226,8 @@ def main_eval_vit(argv=None, variant="vit"):
     print(f"Torch version: {torch.__version__}, device: {torch.cuda.get_device_name(0)}")
     print(f"Evaluation using Rotated IoU for mAP/matching: {args.rotated}")
     print(f"Evaluation using Rotated NMS: {args.rotated_nms}")
+    if args.tta_flip or args.fuse_boxes:
+        print(f"Evaluation using flip TTA: {args.tta_flip}, weighted box fusion: {args.fuse_boxes}")
 
     ckpt = None
     if Path(args.checkpoint).is_file():
@@ -280,7 +300,8 @@ def main_eval_vit(argv=None, variant="vit"):
     dump = None
     if args.attn_maps is not None:
         dump = AttnDump(args.attn_maps, args.attn_top, [int(b) for b in args.attn_blocks.split(",") if b.strip()])
-    results = run_inference(model, loader, anchors, rotated_nms=args.rotated_nms, attn_dump=dump)
+    results = run_inference(model, loader, anchors, rotated_nms=args.rotated_nms, attn_dump=dump,
+                            tta_flip=args.tta_flip, fuse_boxes=args.fuse_boxes)
     torch.cuda.synchronize()
     if dump is not None:
         print(f"Attention maps of {dump.written} batches written to {dump.out_dir}")

@@ -5,6 +5,7 @@ HD-map rasterisation (utils.py:108-182) and the frame ground truth (utils.py:184
 dataset.py builds its samples from."""
 from __future__ import annotations
 
+import ctypes
 import math
 import random
 
@@ -145,6 +146,103 @@ def nms_batched(boxes_list, scores_list, iou_threshold: float = 0.2, rotated: bo
     return [keep[seg[i]: seg[i] + cnt[i]] for i in range(S)]
 
 
+def nms_fuse_batched(boxes_list, scores_list, intents_list, views_list=None, iou_threshold: float = 0.2,
+                     rotated: bool = False, fuse: bool = True, num_classes: int = len(INTENTIONS_MAP)):
+    """nms_batched followed by weighted box fusion (ivit_nms_fuse_batched, include/ivit.h): every
+    suppressed candidate belongs to the kept box (leader) that removed it; with ``fuse`` a leader's
+    box becomes the score-weighted mean of its cluster (each member aligned to the leader's
+    orientation), its intention the weighted vote, its score the mean over the views of the best
+    member score of each view. ``views_list`` (0 / 1 per row) turns the two-view score rule on;
+    None means one view. ``fuse=False`` returns the leaders' own rows, i.e. NMS over the union.
+    Returns per sample {'leaders' (int64 local rows), 'boxes', 'scores', 'intentions' (int64),
+    'members' (int32 cluster sizes)} as device tensors, in descending fused-score order."""
+    ns = [int(b.shape[0]) for b in boxes_list]
+    S, total = len(ns), sum(ns)
+    dev = boxes_list[0].device if S else torch.device("cuda")
+    seg = np.concatenate([[0], np.cumsum(ns)]).astype(np.int64)
+    words = [n * ((n + 63) // 64) for n in ns]
+    moff = np.concatenate([[0], np.cumsum(words)[:-1]]).astype(np.int64) if S else np.zeros((0,), np.int64)
+    lead = torch.empty((total,), dtype=torch.int64, device=dev)
+    ob = torch.empty((total, 5), dtype=torch.float32, device=dev)
+    osc = torch.empty((total,), dtype=torch.float32, device=dev)
+    oi = torch.empty((total,), dtype=torch.int64, device=dev)
+    om = torch.empty((total,), dtype=torch.int32, device=dev)
+    cnt = [0] * S
+    if total > 0:
+        b = torch.cat([x.float().reshape(-1, 5) for x in boxes_list]).contiguous()
+        sc = torch.cat([x.float().reshape(-1) for x in scores_list]).contiguous()
+        it = torch.cat([x.reshape(-1).to(torch.int32) for x in intents_list]).contiguous()
+        vw = None
+        if views_list is not None:
+            vw = torch.cat([x.reshape(-1).to(torch.int32) for x in views_list]).contiguous()
+        if not (sc.numel() == it.numel() == total and (vw is None or vw.numel() == total)):
+            raise ValueError("nms_fuse_batched: boxes, scores, intentions and views must have the same rows")
+        d_seg = torch.from_numpy(seg).to(dev, non_blocking=True)
+        d_moff = torch.from_numpy(moff).to(dev, non_blocking=True)
+        count = torch.empty((S,), dtype=torch.int64, device=dev)
+        ws = workspace(lib.ivit_nms_fuse_batched_workspace(S, total, sum(words), int(rotated)), dev)
+        lib.ivit_nms_fuse_batched(ptr(b), ptr(sc), ptr(it), ptr(vw), ptr(d_seg), ptr(d_moff), S, total, max(ns),
+                                  sum(words), int(num_classes), 1 if vw is None else 2, int(bool(fuse)),
+                                  int(bool(rotated)), float(iou_threshold), ptr(lead), ptr(ob), ptr(osc), ptr(oi),
+                                  ptr(om), ptr(count), ptr(ws), ws.numel(), stream())
+        cnt = count.cpu().tolist()
+    out = []
+    for i in range(S):
+        lo, hi = int(seg[i]), int(seg[i]) + cnt[i]
+        out.append({"leaders": lead[lo:hi], "boxes": ob[lo:hi], "scores": osc[lo:hi], "intentions": oi[lo:hi],
+                    "members": om[lo:hi]})
+    return out
+
+
+def tta_chunk(B: int, V: int, NA: int, rotated: bool = False) -> int:
+    """Samples per ivit_eval_post_tta launch set (the rule in include/ivit.h): the largest Bc whose
+    workspace fits in what ivit_eval_post (rotated: ivit_eval_post_rotated) reserves for the same
+    B x NA batch, at least 1. The mask grows with (V * NA)^2: about B / 4 for two views."""
+    bound = (lib.ivit_eval_post_rotated_workspace if rotated else lib.ivit_eval_post_workspace)(B, NA)
+    lo, hi = 1, max(int(B), 1)
+    while lo < hi:  # the workspace is monotone in the sample count
+        mid = (lo + hi + 1) // 2
+        if lib.ivit_eval_post_tta_workspace(mid, V, NA, int(rotated)) <= bound:
+            lo = mid
+        else:
+            hi = mid - 1
+    return lo
+
+
+def _post_launch_tta(views, anchors, conf_threshold, nms_threshold, rotated_nms=False, fuse_boxes=False, chunk=None):
+    """ivit_eval_post_tta for a batch on the current stream, in chunks of tta_chunk samples (``chunk``
+    overrides it). views: [(cls, box_rel, intent)] of one or two forwards (the second of the mirrored
+    rasters). Returns what _post_collect needs: packed rows of capacity V * NA per sample, the counts
+    and the cluster sizes."""
+    V = len(views)
+    B, NA = views[0][0].shape[0], anchors.shape[0]
+    dev = views[0][0].device
+    cls = [v[0].reshape(B, NA).float() for v in views]
+    box = [v[1].reshape(B, NA, 6).float() for v in views]
+    it = [v[2].reshape(B, NA, -1).float() for v in views]
+    anc = anchors.float().contiguous()
+    K, C = it[0].shape[2], V * NA
+    flip = (ctypes.c_int * K)(*[int(_FLIP_INTENTION[k]) if k < _FLIP_INTENTION.shape[0] else k for k in range(K)])
+    sc = torch.empty((B, C), dtype=torch.float32, device=dev)
+    bx = torch.empty((B, C, 5), dtype=torch.float32, device=dev)
+    ii = torch.empty((B, C), dtype=torch.int64, device=dev)
+    mem = torch.empty((B, C), dtype=torch.int32, device=dev)
+    cnt = torch.empty((B,), dtype=torch.int64, device=dev)
+    Bc = int(chunk) if chunk else tta_chunk(B, V, NA, rotated_nms)
+    ws = workspace(lib.ivit_eval_post_tta_workspace(min(Bc, B), V, NA, int(rotated_nms)), dev)
+    for b0 in range(0, B, Bc):
+        b1 = min(b0 + Bc, B)
+        if V == 1:  # [1, Bc, NA]: a slice of the model's own output, no copy
+            c, r, t = cls[0][b0:b1].contiguous(), box[0][b0:b1].contiguous(), it[0][b0:b1].contiguous()
+        else:
+            c, r, t = (torch.stack([x[b0:b1] for x in xs]) for xs in (cls, box, it))
+        lib.ivit_eval_post_tta(ptr(c), ptr(r), ptr(t), ptr(anc), V, b1 - b0, NA, K, flip, float(conf_threshold),
+                               float(nms_threshold), int(bool(rotated_nms)), int(bool(fuse_boxes)), ptr(sc[b0:b1]),
+                               ptr(bx[b0:b1]), ptr(ii[b0:b1]), ptr(mem[b0:b1]), ptr(cnt[b0:b1]), ptr(ws), ws.numel(),
+                               stream())
+    return sc, bx, ii, cnt, mem
+
+
 def _post_launch(cls_logits, box_preds_rel, intent_logits, anchors, conf_threshold, nms_threshold, rotated_nms=False):
     """ivit_eval_post (ivit_eval_post_rotated with ``rotated_nms``) for a batch on the current stream;
     returns what _post_collect needs."""
@@ -168,29 +266,48 @@ def _post_launch(cls_logits, box_preds_rel, intent_logits, anchors, conf_thresho
 
 
 def _post_collect(launched):
-    sc, bx, ii, cnt = launched
+    sc, bx, ii, cnt = launched[:4]
     n = cnt.cpu().tolist()  # the one host synchronisation
-    return [{"pred_scores": sc[b, : n[b]], "pred_boxes_xywha": bx[b, : n[b]], "pred_intentions": ii[b, : n[b]]}
-            for b in range(len(n))]
+    out = [{"pred_scores": sc[b, : n[b]], "pred_boxes_xywha": bx[b, : n[b]], "pred_intentions": ii[b, : n[b]]}
+           for b in range(len(n))]
+    if len(launched) > 4:  # _post_launch_tta: the cluster sizes
+        for b, p in enumerate(out):
+            p["pred_members"] = launched[4][b, : n[b]]
+    return out
 
 
-def _post_empty(B, dev):
-    return [{"pred_scores": torch.empty((0,), device=dev), "pred_boxes_xywha": torch.empty((0, 5), device=dev),
-             "pred_intentions": torch.empty((0,), dtype=torch.long, device=dev)} for _ in range(B)]
+def _post_empty(B, dev, members=False):
+    out = [{"pred_scores": torch.empty((0,), device=dev), "pred_boxes_xywha": torch.empty((0, 5), device=dev),
+            "pred_intentions": torch.empty((0,), dtype=torch.long, device=dev)} for _ in range(B)]
+    if members:
+        for p in out:
+            p["pred_members"] = torch.empty((0,), dtype=torch.int32, device=dev)
+    return out
 
 
 def postprocess_batch(cls_logits: torch.Tensor, box_preds_rel: torch.Tensor, intent_logits: torch.Tensor,
                       anchors: torch.Tensor, conf_threshold: float = 0.1, nms_threshold: float = 0.2,
-                      rotated_nms: bool = False):
+                      rotated_nms: bool = False, tta_logits=None, fuse_boxes: bool = False, tta_chunk_size=None):
     """eval_vit.py:156-176 for a whole batch on hand-written kernels (ivit_eval_post): sigmoid →
     score >= conf in anchor order → decode → NMS → argmax intention, every sample at once, four
     launches and ONE host read (the kept counts). Returns [{'pred_scores', 'pred_boxes_xywha',
     'pred_intentions'}] per sample as device tensors (views of the packed outputs; the caller
     moves them to the host when it needs them). ``rotated_nms=True`` suppresses on the rotated
-    IoU of the decoded boxes (apply_nms(rotated=True)); everything else is the same."""
+    IoU of the decoded boxes (apply_nms(rotated=True)); everything else is the same.
+    ``tta_logits`` = (cls, box_rel, intent) of the forward on the mirrored rasters (flip_bev_batch)
+    adds that view's candidates, un-mirrored, before the NMS; ``fuse_boxes=True`` replaces every
+    kept box by the weighted fusion of the candidates it suppressed (ivit_eval_post_tta,
+    include/ivit.h). With either, the dicts gain 'pred_members' (int32 cluster sizes) and the batch
+    runs in chunks of tta_chunk samples (``tta_chunk_size`` overrides it); still one host read.
+    Without them the call is the one it always was."""
     B, NA = cls_logits.shape[0], anchors.shape[0]
+    tta = tta_logits is not None or fuse_boxes
     if NA == 0 or B == 0:
-        return _post_empty(B, cls_logits.device)
+        return _post_empty(B, cls_logits.device, members=tta)
+    if tta:
+        views = [(cls_logits, box_preds_rel, intent_logits)] + ([tuple(tta_logits)] if tta_logits is not None else [])
+        return _post_collect(_post_launch_tta(views, anchors, conf_threshold, nms_threshold, rotated_nms, fuse_boxes,
+                                              tta_chunk_size))
     return _post_collect(_post_launch(cls_logits, box_preds_rel, intent_logits, anchors, conf_threshold,
                                       nms_threshold, rotated_nms))
 
@@ -202,11 +319,14 @@ class PostPipeline:
     ~4 ms of mostly serial kernels per B = 32 batch) no longer idles the ViT streams.
     ``push(cls, box, intent)`` returns the previous batch's predictions (None for the first);
     ``flush()`` returns the last one's. Same kernels and results as postprocess_batch
-    (``rotated_nms`` included)."""
+    (``rotated_nms``, ``tta_flip`` and ``fuse_boxes`` included; with ``tta_flip`` push takes the
+    mirrored forward's logits as well)."""
 
-    def __init__(self, anchors, conf_threshold=0.1, nms_threshold=0.2, rotated_nms=False):
+    def __init__(self, anchors, conf_threshold=0.1, nms_threshold=0.2, rotated_nms=False, tta_flip=False,
+                 fuse_boxes=False):
         self.anchors, self.conf, self.nms = anchors, conf_threshold, nms_threshold
         self.rotated_nms = bool(rotated_nms)
+        self.tta_flip, self.fuse_boxes = bool(tta_flip), bool(fuse_boxes)
         self._kw = {"rotated_nms": True} if self.rotated_nms else {}  # the default call is the one it always was
         self.stream = torch.cuda.Stream(anchors.device) if anchors.is_cuda else None
         if self.stream is not None:
@@ -227,22 +347,29 @@ class PostPipeline:
         torch.cuda.current_stream(p[0].device).wait_stream(self.stream)
         return out
 
-    def push(self, cls_logits, box_preds_rel, intent_logits):
+    def _launch(self, cls_logits, box_preds_rel, intent_logits, tta_logits):
+        if self.tta_flip or self.fuse_boxes:
+            views = [(cls_logits, box_preds_rel, intent_logits)] + ([tuple(tta_logits)] if self.tta_flip else [])
+            return _post_launch_tta(views, self.anchors, self.conf, self.nms, self.rotated_nms, self.fuse_boxes)
+        return _post_launch(cls_logits, box_preds_rel, intent_logits, self.anchors, self.conf, self.nms, **self._kw)
+
+    def push(self, cls_logits, box_preds_rel, intent_logits, tta_logits=None):
+        """``tta_logits``: the mirrored forward's (cls, box_rel, intent); needed iff ``tta_flip``."""
+        if self.tta_flip != (tta_logits is not None):
+            raise ValueError("PostPipeline: tta_logits go with tta_flip=True, and only with it")
         prev = self._collect()  # batch k-1: its post-processing ran beside this batch's forward
         B, NA = cls_logits.shape[0], self.anchors.shape[0]
         if NA == 0 or B == 0:
-            self.pending = _post_empty(B, cls_logits.device)
+            self.pending = _post_empty(B, cls_logits.device, members=self.tta_flip or self.fuse_boxes)
             return prev
         if self.stream is None:
-            self.pending = _post_launch(cls_logits, box_preds_rel, intent_logits, self.anchors, self.conf, self.nms,
-                                        **self._kw)
+            self.pending = self._launch(cls_logits, box_preds_rel, intent_logits, tta_logits)
             return prev
-        self.stream.wait_stream(torch.cuda.current_stream(cls_logits.device))  # this batch's forward
-        for t in (cls_logits, box_preds_rel, intent_logits):
+        self.stream.wait_stream(torch.cuda.current_stream(cls_logits.device))  # this batch's forward(s)
+        for t in (cls_logits, box_preds_rel, intent_logits) + (tuple(tta_logits) if tta_logits is not None else ()):
             t.record_stream(self.stream)
         with torch.cuda.stream(self.stream):
-            self.pending = _post_launch(cls_logits, box_preds_rel, intent_logits, self.anchors, self.conf, self.nms,
-                                        **self._kw)
+            self.pending = self._launch(cls_logits, box_preds_rel, intent_logits, tta_logits)
         return prev
 
     def flush(self):
@@ -572,6 +699,24 @@ def augment_bev_batch(lidar_bev: torch.Tensor, map_bev: torch.Tensor, gt_list, o
         params.append(p)
     _run_bev_passes(jobs)
     return lo, mo, gts, params
+
+
+def flip_bev_batch(lidar_bev: torch.Tensor, map_bev: torch.Tensor):
+    """The mirror of random_flip_bev (np.flip on the last axis) for every sample of a device batch
+    ([B, C, H, W] f32 each), out of place: the second view of flip test-time augmentation. One
+    ivit_bev_augment copy pass with the flip in its reads per stack kind (the LiDAR and the map
+    stacks differ in depth). Its detections come back through _FLIP_INTENTION and y, yaw -> -y, -yaw
+    (ivit_eval_post_tta)."""
+    if lidar_bev.dim() != 4 or map_bev.dim() != 4 or lidar_bev.shape[0] != map_bev.shape[0]:
+        raise ValueError("flip_bev_batch takes [B, C, H, W] lidar and map batches")
+    p = {"flip": True, "angle": None, "scale": None, "rects": []}
+    outs = []
+    for x in (lidar_bev, map_bev):
+        src = _bev_in(x)
+        dst = torch.empty_like(src)
+        _run_bev_passes([(src[b], dst[b], p) for b in range(src.shape[0])])
+        outs.append(dst)
+    return outs[0], outs[1]
 
 
 # ---------------------------------------------------------------------------- HD-map raster
