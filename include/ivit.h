@@ -34,10 +34,13 @@ extern "C" {
  *                        0 the LDS-tile form for every epilogue, 1 transposed accumulators for the
  *                        Q-prescale and GELU + GELU' outputs, 2 transposed for all;
  *   IVIT_KNOB_CONV_PANEL (IVIT_CONV_PANEL, default 1): 0 runs the stride-1 bf16 convolutions on the
- *                        128 x 128 engine instead of the panel kernels (the tests compare the two). */
+ *                        128 x 128 engine instead of the panel kernels (the tests compare the two);
+ *   IVIT_KNOB_DROP_SKIP  (IVIT_DROP_SKIP, default 1): 0 makes the *_skip entry points ignore their
+ *                        skip pointer (the DropPath row skip off: every sample is computed). */
 #define IVIT_KNOB_WIDE_EPI 0
 #define IVIT_KNOB_CONV_PANEL 1
-#define IVIT_KNOB_COUNT 2
+#define IVIT_KNOB_DROP_SKIP 2
+#define IVIT_KNOB_COUNT 3
 
 const char* ivit_version(void);
 const char* ivit_last_error(void);
@@ -98,6 +101,34 @@ int ivit_linear_dgrad_gelu_panel(const void* dY, long lddy, long M, long N, long
  * act GELU_D: the same fc2 dgrad with no GELU' evaluation in its epilogue). */
 int ivit_linear_dgrad_mul_panel(const void* dY, long lddy, long M, long N, long K, const void* wpack_t, const void* G,
                                 long ldg, void* dX, long lddx, void* stream);
+/* DropPath row skip (timm Block: x + drop_path(branch), per-sample factor in {0, 1/(1-p)}): the four
+ * entry points above with `skip`, the factors [ceil(M / rps)] of the branch THIS GEMM belongs to
+ * (rps rows per sample, rps > 0). A 144-row panel whose rows all belong to samples with
+ * skip[b] == 0 is not computed: the wide kernels store zeros to its rows of Y (and of Ypre where
+ * they write one) — zeros, not unwritten rows, because the weight gradient and panels that
+ * straddle a kept sample still read them against an exact zero; the LayerNorm kernels run their
+ * epilogue on a zero accumulator (X, Y, mean, rstd / dX, dXs and the dgamma / dbeta sums are
+ * produced for every row). Results equal the plain entry points' up to the sign of an exact zero,
+ * provided the skipped products were finite (a NaN inside a dropped branch no longer spreads).
+ * skip == null, or IVIT_KNOB_DROP_SKIP at 0: exactly the plain entry point (which forwards here).
+ * ivit_linear_resid_ln_fwd_skip: skip is normally the same pointer as scale;
+ * ivit_linear_dgrad_ln_bwd_skip: scale stays the OUTPUT factor of dXs (the hand-off to the
+ * previous branch), skip is the branch of dY. */
+int ivit_linear_resid_ln_fwd_skip(const void* A, long lda, long M, long N, long K, const void* wpack,
+                                  const float* bias, const float* R, long ldr, const float* scale, long rps,
+                                  const float* gamma, const float* beta, float eps, float* X, long ldx, void* Y,
+                                  long ldy, float* mean, float* rstd, const float* skip, void* stream);
+int ivit_linear_dgrad_ln_bwd_skip(const void* dY, long lddy, long M, long N, long K, const void* wpack_t,
+                                  const float* X, long ldx, const float* gamma, const float* mean, const float* rstd,
+                                  const float* dres, long ldr, float* dX, long lddx, void* dXs, const float* scale,
+                                  long rps, float* dgamma, float* dbeta, int accumulate, void* work, long work_bytes,
+                                  const float* skip, void* stream);
+int ivit_linear_fwd_panel_skip(const void* A, long lda, long M, long N, long K, const void* wpack, const float* bias,
+                               int act, long qcols, float qscale, void* Y, long ldy, void* Ypre, long ldpre,
+                               const float* skip, long rps, void* stream);
+int ivit_linear_dgrad_mul_panel_skip(const void* dY, long lddy, long M, long N, long K, const void* wpack_t,
+                                     const void* G, long ldg, void* dX, long lddx, const float* skip, long rps,
+                                     void* stream);
 /* The weight and bias gradients of one timm Block's four linears (Mlp.fc2, Mlp.fc1, Attention.proj,
  * Attention.qkv; model_vit.py:64,71 -> timm Block backward) in one grouped launch + one reduce:
  *   dW_g = dY_g^T X_g (f32 [N][K]), db_g = colsum(dY_g) (f32 [N], may be null), bf16 token-major
@@ -249,6 +280,17 @@ int ivit_attn_fwd_q2(const void* qkv, long B, long N, long H, long Dh, void* out
                      long work_bytes, void* stream);
 int ivit_attn_bwd_q2(const void* qkv, const void* out, const void* dout, const float* lse, long B, long N, long H,
                      long Dh, void* dqkv, void* work, long work_bytes, void* stream);
+/* The same with the DropPath row skip: skip [B] = the attention branch's per-sample factors. The
+ * workgroups of a sample with skip[b] == 0 load nothing and store zeros to their rows of out
+ * (forward) or dqkv (backward); that sample's lse and backward row constants stay unwritten (their
+ * only readers are the skipped workgroups of the same sample). Other samples: bit-identical.
+ * The kept samples' tiles are dealt out evenly over the XCDs (the plain block remap would leave a
+ * dropped sample's XCD idle), so the launch gets shorter by about the dropped share.
+ * skip == null, or IVIT_KNOB_DROP_SKIP at 0: exactly the plain entry point (which forwards here). */
+int ivit_attn_fwd_q2_skip(const void* qkv, long B, long N, long H, long Dh, void* out, float* lse, void* work,
+                          long work_bytes, const float* skip, void* stream);
+int ivit_attn_bwd_q2_skip(const void* qkv, const void* out, const void* dout, const float* lse, long B, long N,
+                          long H, long Dh, void* dqkv, void* work, long work_bytes, const float* skip, void* stream);
 
 /* ---- Attention probabilities of chosen query rows (model_vit.py:64,71 -> timm Attention: the rows
  *      softmax(q k^T / sqrt(Dh)) that a forward hook on timm's attention would read; the reference

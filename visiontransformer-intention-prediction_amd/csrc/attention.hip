@@ -198,16 +198,27 @@ IVIT_DEV float fwd_step_fenced6(const char* kimg, const char* vimg, const bf16x8
 
 // PRE: prescale Q by c2 in the kernel (ivit_attn_fwd, plain qkv); otherwise the Q block of qkv
 // already holds q * c2 (ivit_attn_fwd_q2).
-template <int W, bool PRE>
+// SKIP: the DropPath row skip (attn_block_id_skip); without it the block ids and the code are the
+// plain kernel's and `skip` is not read.
+template <int W, bool PRE, bool SKIP = false>
 __global__ __launch_bounds__(64 * W, 8 / W) void attn_fwd_bf16_v6_kernel(const bf16* __restrict__ qkv, int N, int H,
                                                                         bf16* __restrict__ out,
-                                                                        float* __restrict__ lse, float c2) {
+                                                                        float* __restrict__ lse, float c2,
+                                                                        const float* __restrict__ skip) {
   __shared__ __attribute__((aligned(16))) char smem[2][2][8192];  // [stage][K|V]
   const int tid = threadIdx.x, lane = tid & 63, hl = lane >> 5;
   const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int2 bid = attn_block_id();
+  bool dropped = false;
+  const int2 bid = SKIP ? attn_block_id_skip(skip, H, dropped) : attn_block_id();
   const int z = bid.y, b = z / H, h = z - b * H;
   const int D = H * 64;
+  if (SKIP && dropped) {
+    // out of a dropped sample is still read against a zero factor (the proj GEMM's straddling
+    // panels, the weight gradient): zeros, not unwritten rows. lse stays unwritten: its only reader
+    // is the dQ kernel's workgroups of this same sample, which skip as well.
+    attn_zero_rows<W>(out + (long)b * N * D + h * 64, D, bid.x * (32 * W), N, tid);
+    return;
+  }
   const long ld = 3L * D;
   const bf16* Qb = qkv + (long)b * N * ld + h * 64;
   const bf16* Kb = Qb + D;
@@ -387,22 +398,33 @@ constexpr int BNS = 3;  // LDS stages of the pipelined backward kernels
 // 16). Q / dO images: chunk c of row r at c ^ (r & 6) — conflict-free for the 16x16x32 row reads
 // (16 rows x one chunk per 16-lane group) and for the transposed reads (8 rows x 2 chunks per
 // half-wave); the 32x32 images' swz128 leaves the latter 2-way.
-template <int W>
+template <int W, bool SKIP = false>
 __global__ __launch_bounds__(64 * W, 8 / W) void attn_bwd_dkv_v4_kernel(const bf16* __restrict__ qkv,
                                                                  const bf16* __restrict__ dout,
                                                                  const float* __restrict__ nlse2p,
                                                                  const float* __restrict__ ndeltap, int N, int Npad,
                                                                  int H, bf16* __restrict__ dqkv, float scale,
-                                                                 const bf16* __restrict__ qsrc, int ldq) {
+                                                                 const bf16* __restrict__ qsrc, int ldq,
+                                                                 const float* __restrict__ skip) {
   __shared__ __attribute__((aligned(16))) char smem[BNS][2][8192];  // [stage][Q|dO]
   __shared__ __attribute__((aligned(16))) float srow[BNS][2][AK];  // [stage][-lse2|-delta]
   const int tid = threadIdx.x, lane = tid & 63;
   const int g = lane >> 4, c16 = lane & 15;
   const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int2 bid = attn_block_id();
+  bool dropped = false;
+  const int2 bid = SKIP ? attn_block_id_skip(skip, H, dropped) : attn_block_id();
   const int z = bid.y, b = z / H, h = z - b * H;
   const int D = H * 64;
   const long ld = 3L * D;
+  if (SKIP && dropped) {
+    // dK = dV = 0 (dO of a dropped sample is zero); written, because the qkv data gradient's
+    // straddling panels and the weight gradient read dqkv. The row constants of this sample, which
+    // its dQ workgroups left unwritten, are not read.
+    bf16* base = dqkv + (long)b * N * ld + h * 64;
+    attn_zero_rows<W>(base + D, ld, bid.x * (32 * W), N, tid);
+    attn_zero_rows<W>(base + 2 * D, ld, bid.x * (32 * W), N, tid);
+    return;
+  }
   const bf16* Kb = qkv + (long)b * N * ld + D + h * 64;
   const bf16* Vb = Kb + D;
   const bf16* Qb = qsrc + (long)b * N * ldq + h * 64;  // q' (prescaled): in qkv, or the plain entry's copy
@@ -721,7 +743,7 @@ IVIT_DEV void dq16_tile_masked(const char* kimg, const char* vimg, const bf16x8 
   }
 }
 
-template <int W>
+template <int W, bool SKIP = false>
 __global__ __launch_bounds__(64 * W, 8 / W) void attn_bwd_dq_v4_kernel(const bf16* __restrict__ qkv,
                                                                 const bf16* __restrict__ dout,
                                                                 float* __restrict__ nlse2p,
@@ -729,15 +751,24 @@ __global__ __launch_bounds__(64 * W, 8 / W) void attn_bwd_dq_v4_kernel(const bf1
                                                                 bf16* __restrict__ dqkv, float scale,
                                                                 const bf16* __restrict__ out,
                                                                 const float* __restrict__ lse,
-                                                                const bf16* __restrict__ qsrc, int ldq) {
+                                                                const bf16* __restrict__ qsrc, int ldq,
+                                                                const float* __restrict__ skip) {
   __shared__ __attribute__((aligned(16))) char smem[BNS][2][8192];  // [stage][K|V]
   const int tid = threadIdx.x, lane = tid & 63;
   const int g = lane >> 4, c16 = lane & 15;
   const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int2 bid = attn_block_id();
+  bool dropped = false;
+  const int2 bid = SKIP ? attn_block_id_skip(skip, H, dropped) : attn_block_id();
   const int z = bid.y, b = z / H, h = z - b * H;
   const int D = H * 64;
   const long ld = 3L * D;
+  if (SKIP && dropped) {
+    // dQ = 0, written (read by the qkv data gradient's straddling panels and the weight gradient).
+    // The row constants (-lse2, -delta) of this sample stay unwritten: only the dK/dV workgroups of
+    // the same sample read them, and those skip too; lse and out of the sample are not read.
+    attn_zero_rows<W>(dqkv + (long)b * N * ld + h * 64, ld, bid.x * (32 * W), N, tid);
+    return;
+  }
   const bf16* Kb = qkv + (long)b * N * ld + D + h * 64;
   const bf16* Vb = Kb + D;
   const bf16* Qb = qsrc + (long)b * N * ldq + h * 64;  // q' (prescaled)
@@ -1081,7 +1112,7 @@ void kt_launch(int tag, K kernel, dim3 g, dim3 b, hipStream_t st, Args... args) 
 // qkv (ldq = 3D) on the q2 path, the plain entry's copy (ldq = D) otherwise.
 namespace {
 void attn_bwd_v4_launch(const void* qkv, const void* out, const void* dout, const float* lse, long B, long N, long H,
-                        void* dqkv, float* nlse2p, const void* qsrc, int ldq, hipStream_t st) {
+                        void* dqkv, float* nlse2p, const void* qsrc, int ldq, const float* skip, hipStream_t st) {
   const float scale = 0.125f;  // 1 / sqrt(64)
   const long Npad = (N + AK - 1) / AK * AK;
   float* ndeltap = nlse2p + B * H * Npad;
@@ -1094,12 +1125,13 @@ void attn_bwd_v4_launch(const void* qkv, const void* out, const void* dout, cons
   // the 16x16x32 forms (v4). Same-call A/B against the 32x32x16 v3 kernels they replaced (removed):
   // dK/dV 0.441-0.445 -> 0.406 ms, dQ 0.332-0.334 -> 0.316 ms isolated, step 44.07-44.14 -> 43.29 ms
   // with dK/dV alone (profiles/r05_b_attn_dkv16_ab.txt, r05_c_attn_dq16_ab.txt, r05_c_ab_dkv16_*.json)
-  kt_launch(IVIT_KT_ATTN_BWD_DQ, attn_bwd_dq_v4_kernel<BW>, gw, dim3(64 * BW), st, (const bf16*)qkv,
-            (const bf16*)dout, nlse2p, ndeltap, (int)N, (int)Npad, (int)H, (bf16*)dqkv, scale, (const bf16*)out, lse,
-            (const bf16*)qsrc, ldq);
-  kt_launch(IVIT_KT_ATTN_BWD_DKV, attn_bwd_dkv_v4_kernel<BW>, gw, dim3(64 * BW), st, (const bf16*)qkv,
-            (const bf16*)dout, nlse2p, ndeltap, (int)N, (int)Npad, (int)H, (bf16*)dqkv, 0.69314718055994531f,
-            (const bf16*)qsrc, ldq);
+  // (no skip vector: the instantiations without the DropPath row skip, the kernels as they were)
+  kt_launch(IVIT_KT_ATTN_BWD_DQ, skip ? attn_bwd_dq_v4_kernel<BW, true> : attn_bwd_dq_v4_kernel<BW, false>, gw,
+            dim3(64 * BW), st, (const bf16*)qkv, (const bf16*)dout, nlse2p, ndeltap, (int)N, (int)Npad, (int)H,
+            (bf16*)dqkv, scale, (const bf16*)out, lse, (const bf16*)qsrc, ldq, skip);
+  kt_launch(IVIT_KT_ATTN_BWD_DKV, skip ? attn_bwd_dkv_v4_kernel<BW, true> : attn_bwd_dkv_v4_kernel<BW, false>, gw,
+            dim3(64 * BW), st, (const bf16*)qkv, (const bf16*)dout, nlse2p, ndeltap, (int)N, (int)Npad, (int)H,
+            (bf16*)dqkv, 0.69314718055994531f, (const bf16*)qsrc, ldq, skip);
 }
 }  // namespace
 
@@ -1124,7 +1156,7 @@ extern "C" int ivit_attn_fwd(int dtype, const void* qkv, long B, long N, long H,
     // prescaled-Q kernel with the c2 = log2(e)/sqrt(Dh) multiply done on the Q fragments
     dim3 g(ivit_cdiv(N, 128), B * H);
     hipLaunchKernelGGL((attn_fwd_bf16_v6_kernel<4, true>), g, dim3(256), 0, st, (const bf16*)qkv, (int)N, (int)H,
-                       (bf16*)out, lse, scale * LOG2E);
+                       (bf16*)out, lse, scale * LOG2E, (const float*)nullptr);
     IVIT_LAUNCH_CHECK();
     return 0;
   }
@@ -1161,7 +1193,7 @@ extern "C" int ivit_attn_bwd(int dtype, const void* qkv, const void* out, const 
     bf16* q2 = (bf16*)((char*)work + attn_rows_bytes(B, N, H));
     hipLaunchKernelGGL(attn_prescale_q_kernel, dim3(ivit_cdiv(B * N * D / 8, 256)), dim3(256), 0, st,
                        (const bf16*)qkv, B * N, (int)D, scale * LOG2E, q2);
-    attn_bwd_v4_launch(qkv, out, dout, lse, B, N, H, dqkv, nlse2p, q2, (int)D, st);
+    attn_bwd_v4_launch(qkv, out, dout, lse, B, N, H, dqkv, nlse2p, q2, (int)D, nullptr, st);
     IVIT_LAUNCH_CHECK();
     return 0;
   }
@@ -1253,6 +1285,16 @@ extern "C" int ivit_ktime_read(int tag, double* start_ms, double* stop_ms, long 
 // ------------------------------------------------------------------------- Q-prescaled bf16 path
 extern "C" int ivit_attn_fwd_q2(const void* qkv, long B, long N, long H, long Dh, void* out, float* lse, void* work,
                                 long work_bytes, void* stream) {
+  return ivit_attn_fwd_q2_skip(qkv, B, N, H, Dh, out, lse, work, work_bytes, nullptr, stream);
+}
+
+// The DropPath factors the attention launches skip by: none with IVIT_KNOB_DROP_SKIP at 0.
+static const float* attn_drop_skip(const float* skip) {
+  return ivit_knob(IVIT_KNOB_DROP_SKIP) != 0 ? skip : nullptr;
+}
+
+extern "C" int ivit_attn_fwd_q2_skip(const void* qkv, long B, long N, long H, long Dh, void* out, float* lse,
+                                     void* work, long work_bytes, const float* skip, void* stream) {
   IVIT_CHECK_ARG(Dh == 64, "ivit_attn_fwd_q2: head dim must be 64 (got %ld)", Dh);
   (void)work;
   (void)work_bytes;
@@ -1260,8 +1302,9 @@ extern "C" int ivit_attn_fwd_q2(const void* qkv, long B, long N, long H, long Dh
   dim3 g(ivit_cdiv(N, 128), B * H);
   // (a 16x16x32 form of this kernel measured slower: 0.295-0.302 vs 0.281-0.283 ms isolated, 43.65-43.88
   // vs 42.77-42.83 ms per step, profiles/r05_d_attn_fwd16_ab.txt; removed)
-  kt_launch(IVIT_KT_ATTN_FWD, attn_fwd_bf16_v6_kernel<4, false>, g, dim3(256), ivit_stream(stream), (const bf16*)qkv,
-            (int)N, (int)H, (bf16*)out, lse, 1.0f);
+  skip = attn_drop_skip(skip);
+  kt_launch(IVIT_KT_ATTN_FWD, skip ? attn_fwd_bf16_v6_kernel<4, false, true> : attn_fwd_bf16_v6_kernel<4, false, false>,
+            g, dim3(256), ivit_stream(stream), (const bf16*)qkv, (int)N, (int)H, (bf16*)out, lse, 1.0f, skip);
   IVIT_LAUNCH_CHECK();
   return 0;
 }
@@ -1272,10 +1315,17 @@ extern "C" int ivit_attn_fwd_q2(const void* qkv, long B, long N, long H, long Dh
 // (the gradient w.r.t. the unscaled q); dK = ln2 dS^T q' = scale dS^T q.
 extern "C" int ivit_attn_bwd_q2(const void* qkv, const void* out, const void* dout, const float* lse, long B, long N,
                                 long H, long Dh, void* dqkv, void* work, long work_bytes, void* stream) {
+  return ivit_attn_bwd_q2_skip(qkv, out, dout, lse, B, N, H, Dh, dqkv, work, work_bytes, nullptr, stream);
+}
+
+extern "C" int ivit_attn_bwd_q2_skip(const void* qkv, const void* out, const void* dout, const float* lse, long B,
+                                     long N, long H, long Dh, void* dqkv, void* work, long work_bytes,
+                                     const float* skip, void* stream) {
   IVIT_CHECK_ARG(Dh == 64, "ivit_attn_bwd_q2: head dim must be 64 (got %ld)", Dh);
   IVIT_CHECK_ARG(work_bytes >= attn_rows_bytes(B, N, H), "ivit_attn_bwd_q2: workspace too small");
   if (B * N * H == 0) return 0;
-  attn_bwd_v4_launch(qkv, out, dout, lse, B, N, H, dqkv, (float*)work, qkv, (int)(3 * H * Dh), ivit_stream(stream));
+  attn_bwd_v4_launch(qkv, out, dout, lse, B, N, H, dqkv, (float*)work, qkv, (int)(3 * H * Dh), attn_drop_skip(skip),
+                     ivit_stream(stream));
   IVIT_LAUNCH_CHECK();
   return 0;
 }

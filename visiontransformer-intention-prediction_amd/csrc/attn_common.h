@@ -104,6 +104,61 @@ IVIT_DEV void wave_tile_store(char* lds, const f32x4 (&v)[2][4], float scale, bf
   }
 }
 
+// DropPath row skip: attn_block_id for a launch whose samples with skip[b] == 0 are dropped (their
+// branch factor is exactly 0, so nothing the step returns depends on their workgroups' results).
+// -> (row tile, z = b H + h) and whether that tile belongs to a dropped sample (the workgroup then
+// only stores zeros). Everything here is a function of the block id and of scalar loads of
+// skip[0 .. B-1], so the whole workgroup takes one path, decided before its first DMA or barrier.
+//
+// The plain remap gives XCD x the logical ids [x total / 8, (x + 1) total / 8): at B = 8 that is one
+// whole sample per XCD, and a dropped sample would only idle its XCD while the launch still lasts
+// as long as the seven others. So the KEPT samples' tiles, in their logical order, are dealt out
+// in eight equal contiguous shares, one per XCD, to the first slots of each XCD; the XCDs' remaining
+// slots take the dropped samples' tiles. Bijective; with skip == nullptr, or with no sample dropped,
+// exactly attn_block_id().
+IVIT_DEV int2 attn_block_id_skip(const float* __restrict__ skip, int H, bool& dropped) {
+  dropped = false;
+  if (!skip) return attn_block_id();
+  const int nb = gridDim.x, total = nb * gridDim.y, B = gridDim.y / H, per = nb * H;  // per: tiles of a sample
+  const int orig = blockIdx.x + blockIdx.y * nb;
+  int nkept = 0;
+  for (int b = 0; b < B; ++b) nkept += skip[b] != 0.0f ? 1 : 0;
+  int flat;  // this workgroup's tile among the kept samples' tiles (dropped: among the dropped ones')
+  if (total < 16) {  // as xcd_remap: too few workgroups to deal out
+    const int b = orig / per;
+    dropped = skip[b] == 0.0f;
+    return make_int2(orig % nb, orig / nb);
+  } else {
+    const int x = orig % 8, slot = orig / 8;
+    const int q = total / 8, r = total % 8, kq = nkept * per / 8, kr = nkept * per % 8;
+    const int first = x * q + min(x, r);        // first logical id of XCD x in the plain remap
+    const int kfirst = x * kq + min(x, kr);     // first kept tile of XCD x
+    const int kshare = kq + (x < kr ? 1 : 0);   // kept tiles of XCD x (<= its slots)
+    dropped = slot >= kshare;
+    flat = dropped ? first - kfirst + slot - kshare : kfirst + slot;
+  }
+  // the (flat / per)-th kept (dropped) sample, in sample order
+  int rank = flat / per, b = 0;
+  for (int i = 0; i < B; ++i) {
+    const bool mine = (skip[i] == 0.0f) == dropped;
+    if (mine && rank == 0) b = i;
+    rank -= mine ? 1 : 0;
+  }
+  const int id = __builtin_amdgcn_readfirstlane(b * per + flat % per);
+  return make_int2(id % nb, id / nb);
+}
+
+// ... and what such a workgroup (64 W threads) stores instead: zeros to its [32 W rows][64 columns]
+// block, rows row0 + k < nrows at dst + (row0 + k) * ld, as the 16-B row chunks the epilogues store.
+template <int W>
+IVIT_DEV void attn_zero_rows(bf16* dst, long ld, int row0, int nrows, int tid) {
+#pragma unroll
+  for (int k = 0; k < 4; ++k) {
+    const int i = tid + k * 64 * W, row = row0 + (i >> 3);
+    if (row < nrows) *(uint4*)(dst + (long)row * ld + 8 * (i & 7)) = make_uint4(0u, 0u, 0u, 0u);
+  }
+}
+
 IVIT_DEV f32x4 mfma16(const bf16x8& a, const bf16x8& b, const f32x4& c) {
   return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0);
 }

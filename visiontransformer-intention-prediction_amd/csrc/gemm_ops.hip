@@ -27,13 +27,14 @@ void ivit_set_error(const char* fmt, ...) {
 }
 extern "C" const char* ivit_last_error(void) { return g_err; }
 
-// Tuning knobs: defaults, then the IVIT_WIDE_EPI / IVIT_CONV_PANEL environment variables read ONCE
-// when the library loads; ivit_set_knob changes them at run time (tests, A/B tools).
+// Tuning knobs: defaults, then the IVIT_WIDE_EPI / IVIT_CONV_PANEL / IVIT_DROP_SKIP environment
+// variables read ONCE when the library loads; ivit_set_knob changes them at run time (tests, A/B tools).
 static int knob_env(const char* name, int dflt) {
   const char* v = getenv(name);
   return v ? atoi(v) : dflt;
 }
-static int g_knobs[IVIT_KNOB_COUNT] = {knob_env("IVIT_WIDE_EPI", 0), knob_env("IVIT_CONV_PANEL", 1)};
+static int g_knobs[IVIT_KNOB_COUNT] = {knob_env("IVIT_WIDE_EPI", 0), knob_env("IVIT_CONV_PANEL", 1),
+                                       knob_env("IVIT_DROP_SKIP", 1)};
 int ivit_knob(int knob) { return knob >= 0 && knob < IVIT_KNOB_COUNT ? g_knobs[knob] : 0; }
 extern "C" int ivit_set_knob(int knob, int value) {
   IVIT_CHECK_ARG(knob >= 0 && knob < IVIT_KNOB_COUNT, "ivit_set_knob: unknown knob %d", knob);

@@ -55,6 +55,19 @@ IVIT_DEV PanelA panel_a_setup(const bf16* A, long lda, int M, int m0, int wv, in
   return p;
 }
 
+// DropPath row skip: true when every sample that owns a row of the panel (m0 .. min(m0 + 143, M - 1),
+// rps rows per sample; more than two samples when rps < 144) has the branch factor skip[b] == 0, so
+// the panel's GEMM result is multiplied by zero downstream. Workgroup-uniform: m0 comes from the
+// block id and skip[.] is read by scalar loads, so a caller branches on it before its first barrier
+// or LDS-DMA and all waves keep one barrier / vmcnt cadence. skip == nullptr: never.
+IVIT_DEV bool panel_dropped(const float* __restrict__ skip, int rps, int m0, int M) {
+  if (!skip) return false;
+  const int b1 = (min(m0 + RP_MT, M) - 1) / rps;
+  int kept = 0;
+  for (int b = m0 / rps; b <= b1; ++b) kept |= skip[b] != 0.0f ? 1 : 0;
+  return __builtin_amdgcn_readfirstlane(kept) == 0;
+}
+
 // acc[9][3] = rows m0 .. m0+143 of A (K = 64 KT) times the 48 columns of 16-column blocks
 // nb0 .. nb0+2 of a packed weight with NB16 blocks in total.
 // TR: the MFMA operands swapped (weights as A, the panel as B), so acc holds the output
@@ -156,7 +169,7 @@ __global__ __launch_bounds__(512, 1) void rowpanel_ln_kernel(
     const float* __restrict__ bias, const float* R, long ldr, const float* __restrict__ scale, int rps,
     const float* __restrict__ gamma, const float* __restrict__ beta, float eps, float* X, long ldx,
     bf16* __restrict__ Y, long ldy, float* mean, float* rstd, float* dX, long lddx, float* __restrict__ part,
-    u64* stamps) {
+    const float* __restrict__ skip, u64* stamps) {
   __shared__ __attribute__((aligned(16))) char smem[RP_NS * RP_STAGE];
   const int tid = threadIdx.x, lane = tid & 63;
   const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -164,9 +177,21 @@ __global__ __launch_bounds__(512, 1) void rowpanel_ln_kernel(
   Stamps stp;
   if constexpr (ST) stp.begin();
 
-  PanelA pa = panel_a_setup(A, lda, M, m0, wv, lane);
   f32x4 acc[RP_MB][NBW];
-  panel_mainloop(acc, smem, pa, wpack, RP_N / 16, wv * NBW, K / 64, wv, lane, ST ? &stp.t1 : nullptr);
+  if (panel_dropped(skip, rps, m0, M)) {
+    // DropPath row skip (skip = this GEMM's own branch factors): the panel's A rows are exact zeros
+    // (forward: o / a of dropped samples; backward: dh / dqkv), so the product is the zero
+    // accumulator without streaming it. The epilogue runs unchanged: the forward's X, Y, mean and
+    // rstd feed the next branch, the backward gives dX = dres and adds zeros to the partials.
+#pragma unroll
+    for (int i = 0; i < RP_MB; ++i)
+#pragma unroll
+      for (int j = 0; j < NBW; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
+    if constexpr (ST) stp.t1 = clk_now();
+  } else {
+    const PanelA pa = panel_a_setup(A, lda, M, m0, wv, lane);
+    panel_mainloop(acc, smem, pa, wpack, RP_N / 16, wv * NBW, K / 64, wv, lane, ST ? &stp.t1 : nullptr);
+  }
   if constexpr (ST) stp.t2 = clk_now();
 
   // ---- epilogue, one 16-row block at a time through LDS
@@ -466,7 +491,9 @@ __global__ __launch_bounds__(64 * W, 8 / W) void rowpanel_wide_kernel(const bf16
                                                                       int K, const u32x4* __restrict__ wpack, int N,
                                                                       const float* __restrict__ bias, int qcols,
                                                                       float qscale, bf16* __restrict__ Y, long ldy,
-                                                                      bf16* __restrict__ P, long ldp, u64* stamps) {
+                                                                      bf16* __restrict__ P, long ldp,
+                                                                      const float* __restrict__ skip, int rps,
+                                                                      u64* stamps) {
   Stamps stp;
   if constexpr (ST) stp.begin();
   constexpr int CW = 48 * W, TLD = CW + 4, LPR = CW / 12;  // chunk width, T row stride, lanes per row
@@ -486,6 +513,27 @@ __global__ __launch_bounds__(64 * W, 8 / W) void rowpanel_wide_kernel(const bf16
     nc_end = nc_begin + 1;
   }
   const int m0 = rp * RP_MT;
+  if (panel_dropped(skip, rps, m0, M)) {
+    // DropPath row skip: every row of the panel belongs to a dropped sample. Zeros, not unwritten
+    // rows: Y (and the P written beside it) of a dropped sample is still read with a zero on the
+    // other side — a / dh / dqkv / o-side operands by the grouped weight gradient, P (GELU') by the
+    // fc2 data gradient of a panel that straddles a kept sample — and 0 x garbage could be NaN.
+    const int rows = min(RP_MT, M - m0);
+    constexpr int WPR = CW / 4;  // 8-B words per chunk row (Y, P are 8-B aligned, ld % 4 == 0)
+    for (int nc = nc_begin; nc < nc_end; ++nc)
+      for (int i = tid; i < rows * WPR; i += 64 * W) {
+        const int rr = i / WPR, c = nc * CW + (i - rr * WPR) * 4;
+        *(uint2*)(Y + (long)(m0 + rr) * ldy + c) = make_uint2(0u, 0u);
+        if constexpr (epi_writes_p(EPI)) {
+          if (P) *(uint2*)(P + (long)(m0 + rr) * ldp + c) = make_uint2(0u, 0u);
+        }
+      }
+    if constexpr (ST) {
+      stp.t1 = stp.t2 = clk_now();
+      stp.end(stamps);
+    }
+    return;
+  }
   const PanelA pa = panel_a_setup<W>(A, lda, M, m0, wv, lane);
   const int r = tid / LPR, c0 = (tid % LPR) * 12;  // row phase: LPR lanes per row, 12 columns each
   float* T = (float*)smem;                          // [16][TLD] after the main loop
@@ -594,6 +642,8 @@ __global__ __launch_bounds__(64 * W, 8 / W) void rowpanel_wide_kernel(const bf16
 using namespace ivit;
 
 namespace {
+// The DropPath factors a launch skips by: none with IVIT_KNOB_DROP_SKIP at 0.
+const float* drop_skip(const float* skip) { return ivit_knob(IVIT_KNOB_DROP_SKIP) != 0 ? skip : nullptr; }
 template <bool BWD>
 auto ln_kernel(bool st) {
   return st ? rowpanel_ln_kernel<BWD, true> : rowpanel_ln_kernel<BWD, false>;
@@ -607,12 +657,14 @@ auto ln_kernel(bool st) {
 // ivit_set_knob(IVIT_KNOB_WIDE_EPI) (the tests cover every form).
 template <int EPI>
 void launch_wide(dim3 g, hipStream_t st, bool ev1, u64* sb, const bf16* A, long lda, int M, int K, const u32x4* wp,
-                 int N, const float* bias, int qcols, float qscale, bf16* Y, long ldy, bf16* P, long ldp) {
+                 int N, const float* bias, int qcols, float qscale, bf16* Y, long ldy, bf16* P, long ldp,
+                 const float* skip, long rps) {
   const int mode = ivit_knob(IVIT_KNOB_WIDE_EPI);
   ev1 = ev1 && mode != 0 && (EPI == EPI_QS || EPI == EPI_GELUD || mode == 2);
   auto k = ev1 ? (sb ? rowpanel_wide_kernel<EPI, 4, true, 1> : rowpanel_wide_kernel<EPI, 4, false, 1>)
                : (sb ? rowpanel_wide_kernel<EPI, 4, true, 0> : rowpanel_wide_kernel<EPI, 4, false, 0>);
-  hipLaunchKernelGGL(k, g, dim3(256), 0, st, A, lda, M, K, wp, N, bias, qcols, qscale, Y, ldy, P, ldp, sb);
+  hipLaunchKernelGGL(k, g, dim3(256), 0, st, A, lda, M, K, wp, N, bias, qcols, qscale, Y, ldy, P, ldp,
+                     drop_skip(skip), (int)rps, sb);
 }
 bool al16_rows(const void* p, long ld) { return p == nullptr || (((uintptr_t)p & 15) == 0 && ld % 8 == 0); }
 }  // namespace
@@ -621,6 +673,15 @@ extern "C" int ivit_linear_resid_ln_fwd(const void* A, long lda, long M, long N,
                                         const float* bias, const float* R, long ldr, const float* scale, long rps,
                                         const float* gamma, const float* beta, float eps, float* X, long ldx, void* Y,
                                         long ldy, float* mean, float* rstd, void* stream) {
+  return ivit_linear_resid_ln_fwd_skip(A, lda, M, N, K, wpack, bias, R, ldr, scale, rps, gamma, beta, eps, X, ldx, Y,
+                                       ldy, mean, rstd, nullptr, stream);
+}
+
+extern "C" int ivit_linear_resid_ln_fwd_skip(const void* A, long lda, long M, long N, long K, const void* wpack,
+                                             const float* bias, const float* R, long ldr, const float* scale,
+                                             long rps, const float* gamma, const float* beta, float eps, float* X,
+                                             long ldx, void* Y, long ldy, float* mean, float* rstd,
+                                             const float* skip, void* stream) {
   IVIT_CHECK_ARG(N == RP_N, "ivit_linear_resid_ln_fwd: N must be %d (got %ld)", RP_N, N);
   IVIT_CHECK_ARG(M > 0 && K > 0 && K % 64 == 0, "ivit_linear_resid_ln_fwd: K must be a positive multiple of 64");
   IVIT_CHECK_ARG(lda >= K && lda % 8 == 0 && ldr >= N && ldr % 4 == 0 && ldx >= N && ldx % 4 == 0 && ldy >= N &&
@@ -634,7 +695,7 @@ extern "C" int ivit_linear_resid_ln_fwd(const void* A, long lda, long M, long N,
   hipLaunchKernelGGL(ln_kernel<false>(sb != nullptr), dim3(ivit_cdiv(M, RP_MT)),
                      dim3(512), 0, ivit_stream(stream), (const bf16*)A, lda, (int)M, (int)K, (const u32x4*)wpack,
                      bias, R, ldr, scale, (int)rps, gamma, beta, eps, X, ldx, (bf16*)Y, ldy, mean, rstd, nullptr, 0L,
-                     nullptr, sb);
+                     nullptr, drop_skip(skip), sb);
   IVIT_LAUNCH_CHECK();
   return 0;
 }
@@ -646,6 +707,16 @@ extern "C" int ivit_linear_dgrad_ln_bwd(const void* dY, long lddy, long M, long 
                                         const float* rstd, const float* dres, long ldr, float* dX, long lddx,
                                         void* dXs, const float* scale, long rps, float* dgamma, float* dbeta,
                                         int accumulate, void* work, long work_bytes, void* stream) {
+  return ivit_linear_dgrad_ln_bwd_skip(dY, lddy, M, N, K, wpack_t, X, ldx, gamma, mean, rstd, dres, ldr, dX, lddx, dXs,
+                                       scale, rps, dgamma, dbeta, accumulate, work, work_bytes, nullptr, stream);
+}
+
+extern "C" int ivit_linear_dgrad_ln_bwd_skip(const void* dY, long lddy, long M, long N, long K, const void* wpack_t,
+                                             const float* X, long ldx, const float* gamma, const float* mean,
+                                             const float* rstd, const float* dres, long ldr, float* dX, long lddx,
+                                             void* dXs, const float* scale, long rps, float* dgamma, float* dbeta,
+                                             int accumulate, void* work, long work_bytes, const float* skip,
+                                             void* stream) {
   IVIT_CHECK_ARG(N == RP_N, "ivit_linear_dgrad_ln_bwd: N must be %d (got %ld)", RP_N, N);
   IVIT_CHECK_ARG(M > 0 && K > 0 && K % 64 == 0, "ivit_linear_dgrad_ln_bwd: K must be a positive multiple of 64");
   IVIT_CHECK_ARG(lddy >= K && lddy % 8 == 0 && ldx >= N && ldx % 4 == 0 && lddx >= N && lddx % 4 == 0 &&
@@ -662,7 +733,7 @@ extern "C" int ivit_linear_dgrad_ln_bwd(const void* dY, long lddy, long M, long 
   hipLaunchKernelGGL(ln_kernel<true>(sb != nullptr), dim3(nb), dim3(512), 0, st,
                      (const bf16*)dY, lddy, (int)M, (int)K, (const u32x4*)wpack_t, nullptr, dres, ldr, scale,
                      (int)rps, gamma, nullptr, 0.f, (float*)X, ldx, (bf16*)dXs, (long)RP_N, (float*)mean,
-                     (float*)rstd, dX, lddx, (float*)work, sb);
+                     (float*)rstd, dX, lddx, (float*)work, drop_skip(skip), sb);
   IVIT_LAUNCH_CHECK();
   launch_colreduce(st, (const float*)work, nb, 2 * N, (int)(2 * N), dgamma, (int)N, dbeta, accumulate);
   IVIT_LAUNCH_CHECK();
@@ -672,6 +743,14 @@ extern "C" int ivit_linear_dgrad_ln_bwd(const void* dY, long lddy, long M, long 
 extern "C" int ivit_linear_fwd_panel(const void* A, long lda, long M, long N, long K, const void* wpack,
                                      const float* bias, int act, long qcols, float qscale, void* Y, long ldy,
                                      void* Ypre, long ldpre, void* stream) {
+  return ivit_linear_fwd_panel_skip(A, lda, M, N, K, wpack, bias, act, qcols, qscale, Y, ldy, Ypre, ldpre, nullptr, 1,
+                                    stream);
+}
+
+extern "C" int ivit_linear_fwd_panel_skip(const void* A, long lda, long M, long N, long K, const void* wpack,
+                                          const float* bias, int act, long qcols, float qscale, void* Y, long ldy,
+                                          void* Ypre, long ldpre, const float* skip, long rps, void* stream) {
+  IVIT_CHECK_ARG(!skip || rps > 0, "ivit_linear_fwd_panel_skip: rps must be positive (got %ld)", rps);
   IVIT_CHECK_ARG(M > 0 && N > 0 && N % RP_N == 0 && K > 0 && K % 64 == 0 && qcols % RP_N == 0,
                  "ivit_linear_fwd_panel: N and qcols must be multiples of %d, K of 64", RP_N);
   IVIT_CHECK_ARG(act == IVIT_ACT_NONE || ((act == IVIT_ACT_GELU || act == IVIT_ACT_GELU_D) && qcols == 0),
@@ -687,13 +766,15 @@ extern "C" int ivit_linear_fwd_panel(const void* A, long lda, long M, long N, lo
   u64* sb = ivit_stamp_buffer(g.x);
   if (act == IVIT_ACT_GELU_D)
     launch_wide<EPI_GELUD>(g, st, al16_rows(Y, ldy) && al16_rows(Ypre, ldpre), sb, (const bf16*)A, lda, (int)M,
-                           (int)K, (const u32x4*)wpack, (int)N, bias, 0, 1.f, (bf16*)Y, ldy, (bf16*)Ypre, ldpre);
+                           (int)K, (const u32x4*)wpack, (int)N, bias, 0, 1.f, (bf16*)Y, ldy, (bf16*)Ypre, ldpre, skip,
+                          rps);
   else if (act == IVIT_ACT_GELU)
     launch_wide<EPI_GELU>(g, st, al16_rows(Y, ldy) && al16_rows(Ypre, ldpre), sb, (const bf16*)A, lda, (int)M,
-                          (int)K, (const u32x4*)wpack, (int)N, bias, 0, 1.f, (bf16*)Y, ldy, (bf16*)Ypre, ldpre);
+                          (int)K, (const u32x4*)wpack, (int)N, bias, 0, 1.f, (bf16*)Y, ldy, (bf16*)Ypre, ldpre, skip,
+                          rps);
   else
     launch_wide<EPI_QS>(g, st, al16_rows(Y, ldy), sb, (const bf16*)A, lda, (int)M, (int)K, (const u32x4*)wpack,
-                        (int)N, bias, (int)qcols, qscale, (bf16*)Y, ldy, nullptr, 0L);
+                        (int)N, bias, (int)qcols, qscale, (bf16*)Y, ldy, nullptr, 0L, skip, rps);
   IVIT_LAUNCH_CHECK();
   return 0;
 }
@@ -711,13 +792,21 @@ extern "C" int ivit_linear_dgrad_gelu_panel(const void* dY, long lddy, long M, l
   const dim3 g(ivit_cdiv(M, RP_MT) * (N / 192));
   u64* sb = ivit_stamp_buffer(g.x);
   launch_wide<EPI_DGELU>(g, ivit_stream(stream), al16_rows(dX, lddx), sb, (const bf16*)dY, lddy, (int)M, (int)K,
-                         (const u32x4*)wpack_t, (int)N, nullptr, 0, 1.f, (bf16*)dX, lddx, (bf16*)pre, ldpre);
+                         (const u32x4*)wpack_t, (int)N, nullptr, 0, 1.f, (bf16*)dX, lddx, (bf16*)pre, ldpre, nullptr,
+                         1L);
   IVIT_LAUNCH_CHECK();
   return 0;
 }
 
 extern "C" int ivit_linear_dgrad_mul_panel(const void* dY, long lddy, long M, long N, long K, const void* wpack_t,
                                            const void* G, long ldg, void* dX, long lddx, void* stream) {
+  return ivit_linear_dgrad_mul_panel_skip(dY, lddy, M, N, K, wpack_t, G, ldg, dX, lddx, nullptr, 1, stream);
+}
+
+extern "C" int ivit_linear_dgrad_mul_panel_skip(const void* dY, long lddy, long M, long N, long K, const void* wpack_t,
+                                                const void* G, long ldg, void* dX, long lddx, const float* skip,
+                                                long rps, void* stream) {
+  IVIT_CHECK_ARG(!skip || rps > 0, "ivit_linear_dgrad_mul_panel_skip: rps must be positive (got %ld)", rps);
   IVIT_CHECK_ARG(M > 0 && N > 0 && N % RP_N == 0 && K > 0 && K % 64 == 0,
                  "ivit_linear_dgrad_mul_panel: N must be a multiple of %d, K of 64", RP_N);
   IVIT_CHECK_ARG(lddy >= K && lddy % 8 == 0 && lddx >= N && lddx % 4 == 0 && ldg >= N && ldg % 4 == 0,
@@ -729,7 +818,7 @@ extern "C" int ivit_linear_dgrad_mul_panel(const void* dY, long lddy, long M, lo
   const dim3 g(ivit_cdiv(M, RP_MT) * (N / 192));
   u64* sb = ivit_stamp_buffer(g.x);
   launch_wide<EPI_DMUL>(g, ivit_stream(stream), al16_rows(dX, lddx), sb, (const bf16*)dY, lddy, (int)M, (int)K,
-                        (const u32x4*)wpack_t, (int)N, nullptr, 0, 1.f, (bf16*)dX, lddx, (bf16*)G, ldg);
+                        (const u32x4*)wpack_t, (int)N, nullptr, 0, 1.f, (bf16*)dX, lddx, (bf16*)G, ldg, skip, rps);
   IVIT_LAUNCH_CHECK();
   return 0;
 }

@@ -182,15 +182,30 @@ def layernorm_fwd(x, g, b, eps, out_dtype, rowmap=(0, 0, 0), M=None):
     return y, mean, rstd
 
 
-def linear_resid_ln_fwd(a, w, b, resid, row_scale, rps, g, beta, eps):
+def _skip_check(skip, M, rps):
+    """A DropPath row-skip vector (the *_skip entry points): f32 device factors, one per sample."""
+    assert skip.dtype == torch.float32 and skip.is_contiguous() and rps > 0 and skip.numel() * rps >= M, \
+        (skip.dtype, tuple(skip.shape), M, rps)
+    return skip
+
+
+def linear_resid_ln_fwd(a, w, b, resid, row_scale, rps, g, beta, eps, skip=False):
     """bf16 a [M, K] @ w[384, K]^T + b, times row_scale[m / rps], plus the f32 residual → x (f32),
-    then LayerNorm(x) → y (bf16), mean, rstd: one kernel (ivit_linear_resid_ln_fwd)."""
+    then LayerNorm(x) → y (bf16), mean, rstd: one kernel (ivit_linear_resid_ln_fwd). skip: row
+    panels whose samples all have row_scale 0 are not multiplied (DropPath row skip; a's rows of
+    those samples are zeros)."""
     M, K = a.shape
     N = w.shape[0]
     x = torch.empty((M, N), dtype=torch.float32, device=a.device)
     y = torch.empty((M, N), dtype=torch.bfloat16, device=a.device)
     mean = torch.empty((M,), dtype=torch.float32, device=a.device)
     rstd = torch.empty((M,), dtype=torch.float32, device=a.device)
+    if skip and row_scale is not None:
+        _skip_check(row_scale, M, rps)
+        lib.ivit_linear_resid_ln_fwd_skip(ptr(a), a.stride(0), M, N, K, ptr(packed_weight(w)), ptr(b), ptr(resid),
+                                          resid.stride(0), ptr(row_scale), rps, ptr(g), ptr(beta), eps, ptr(x), N,
+                                          ptr(y), N, ptr(mean), ptr(rstd), ptr(row_scale), stream())
+        return x, y, mean, rstd
     lib.ivit_linear_resid_ln_fwd(ptr(a), a.stride(0), M, N, K, ptr(packed_weight(w)), ptr(b), ptr(resid),
                                  resid.stride(0), ptr(row_scale), rps, ptr(g), ptr(beta), eps, ptr(x), N, ptr(y), N,
                                  ptr(mean), ptr(rstd), stream())
@@ -198,11 +213,12 @@ def linear_resid_ln_fwd(a, w, b, resid, row_scale, rps, g, beta, eps):
 
 
 def linear_dgrad_ln_bwd(dy, w, x, g, mean, rstd, dres=None, dx=None, xs_dtype=None, row_scale=None, rps=1,
-                        dg=None, db=None):
+                        dg=None, db=None, skip=None):
     """dgrad G = dy [M, K] (bf16) @ w [K, 384] with the LayerNorm backward of (x, g, mean, rstd) in
     the epilogue: dx = dres + LN_bwd(G) (f32, may alias dres), optional bf16 dxs = dx * row_scale,
     dgamma, dbeta (into ``dg`` / ``db`` when given) — one kernel + the column reduction
-    (ivit_linear_dgrad_ln_bwd)."""
+    (ivit_linear_dgrad_ln_bwd). skip: the DropPath factors of dy's own branch, rps rows per sample
+    (row panels of dropped samples, whose dy rows are zeros, are not multiplied)."""
     M, K = dy.shape
     N = w.shape[1]
     if dx is None:
@@ -211,6 +227,14 @@ def linear_dgrad_ln_bwd(dy, w, x, g, mean, rstd, dres=None, dx=None, xs_dtype=No
     dg = torch.empty((N,), dtype=torch.float32, device=dy.device) if dg is None else dg
     db = torch.empty((N,), dtype=torch.float32, device=dy.device) if db is None else db
     ws = workspace(lib.ivit_linear_dgrad_ln_bwd_workspace(M, N), dy.device)
+    if skip is not None:
+        _skip_check(skip, M, rps)
+        lib.ivit_linear_dgrad_ln_bwd_skip(ptr(dy), dy.stride(0), M, N, K, ptr(packed_weight_t(w)), ptr(x), x.stride(0),
+                                          ptr(g), ptr(mean), ptr(rstd), ptr(dres),
+                                          dres.stride(0) if dres is not None else N, ptr(dx), dx.stride(0), ptr(dxs),
+                                          ptr(row_scale), rps, ptr(dg), ptr(db), 0, ptr(ws), ws.numel(), ptr(skip),
+                                          stream())
+        return dx, dxs, dg, db
     lib.ivit_linear_dgrad_ln_bwd(ptr(dy), dy.stride(0), M, N, K, ptr(packed_weight_t(w)), ptr(x), x.stride(0), ptr(g),
                                  ptr(mean), ptr(rstd), ptr(dres), dres.stride(0) if dres is not None else N, ptr(dx),
                                  dx.stride(0), ptr(dxs), ptr(row_scale), rps, ptr(dg), ptr(db), 0, ptr(ws),
@@ -393,37 +417,52 @@ def qkv_fwd_q2(x, w, b, D):
     return out
 
 
-def panel_fwd(x, w, b, act=ACT_NONE, want_pre=False, qcols=0, qscale=1.0):
+def panel_fwd(x, w, b, act=ACT_NONE, want_pre=False, qcols=0, qscale=1.0, skip=None, rps=1):
     """Row-panel form of a wide bf16 token GEMM (ivit_linear_fwd_panel): x [M, K] bf16 @ w [N, K]
     (f32 master, packed) + b; act GELU with the pre-activation copy (act GELU_D: with GELU' of the
-    pre-activation instead, what the backward needs), or columns < qcols scaled."""
+    pre-activation instead, what the backward needs), or columns < qcols scaled. skip: the DropPath
+    factors of the branch this GEMM belongs to, rps rows per sample — row panels of dropped samples
+    come out as zeros (ivit_linear_fwd_panel_skip)."""
     M, K = x.shape
     N = w.shape[0]
     y = torch.empty((M, N), dtype=torch.bfloat16, device=x.device)
     pre = torch.empty((M, N), dtype=torch.bfloat16, device=x.device) if want_pre else None
+    if skip is not None:
+        lib.ivit_linear_fwd_panel_skip(ptr(x), x.stride(0), M, N, K, ptr(packed_weight(w)), ptr(b), act, qcols, qscale,
+                                       ptr(y), N, ptr(pre), N, ptr(_skip_check(skip, M, rps)), rps, stream())
+        return y, pre
     lib.ivit_linear_fwd_panel(ptr(x), x.stride(0), M, N, K, ptr(packed_weight(w)), ptr(b), act, qcols, qscale,
                               ptr(y), N, ptr(pre), N, stream())
     return y, pre
 
 
-def panel_dgrad(dy, w):
+def panel_dgrad(dy, w, skip=None, rps=1):
     """dy [M, K] bf16 @ w [K, N] (f32 master [out, in], packed transposed) → bf16 [M, N]: the plain
-    dgrad through the row-panel kernel (ivit_linear_fwd_panel on the transposed pack)."""
+    dgrad through the row-panel kernel (ivit_linear_fwd_panel on the transposed pack; skip / rps as
+    for panel_fwd)."""
     M, K = dy.shape
     N = w.shape[1]
     dx = torch.empty((M, N), dtype=torch.bfloat16, device=dy.device)
+    if skip is not None:
+        lib.ivit_linear_fwd_panel_skip(ptr(dy), dy.stride(0), M, N, K, ptr(packed_weight_t(w)), None, ACT_NONE, 0, 1.0,
+                                       ptr(dx), N, None, 0, ptr(_skip_check(skip, M, rps)), rps, stream())
+        return dx
     lib.ivit_linear_fwd_panel(ptr(dy), dy.stride(0), M, N, K, ptr(packed_weight_t(w)), None, ACT_NONE, 0, 1.0,
                               ptr(dx), N, None, 0, stream())
     return dx
 
 
-def panel_dgrad_mul(dy, w, g):
+def panel_dgrad_mul(dy, w, g, skip=None, rps=1):
     """dy [M, K] bf16 @ w [K, N] (f32 master, packed transposed) * g → bf16 [M, N], g = the GELU'
     panel_fwd(act=ACT_GELU_D) wrote (ivit_linear_dgrad_mul_panel: fc2 dgrad into fc1's pre-activation
-    with no GELU' evaluation)."""
+    with no GELU' evaluation; skip / rps as for panel_fwd)."""
     M, K = dy.shape
     N = w.shape[1]
     dx = torch.empty((M, N), dtype=torch.bfloat16, device=dy.device)
+    if skip is not None:
+        lib.ivit_linear_dgrad_mul_panel_skip(ptr(dy), dy.stride(0), M, N, K, ptr(packed_weight_t(w)), ptr(g),
+                                             g.stride(0), ptr(dx), N, ptr(_skip_check(skip, M, rps)), rps, stream())
+        return dx
     lib.ivit_linear_dgrad_mul_panel(ptr(dy), dy.stride(0), M, N, K, ptr(packed_weight_t(w)), ptr(g), g.stride(0),
                                     ptr(dx), N, stream())
     return dx
@@ -440,23 +479,34 @@ def panel_dgrad_gelu(dy, w, pre):
     return dx
 
 
-def attn_fwd_q2(qkv, B, N, H):
+def attn_fwd_q2(qkv, B, N, H, skip=None):
+    """skip: the attention branch's DropPath factors [B] — samples with factor 0 get out = 0 and
+    an unwritten lse (ivit_attn_fwd_q2_skip)."""
     D = H * 64
     out = torch.empty((B * N, D), dtype=qkv.dtype, device=qkv.device)
     lse = torch.empty((B, H, N), dtype=torch.float32, device=qkv.device)
     ev = KernelTimer.span("attn_fwd")
-    lib.ivit_attn_fwd_q2(ptr(qkv), B, N, H, 64, ptr(out), ptr(lse), None, 0, stream())
+    if skip is not None:
+        lib.ivit_attn_fwd_q2_skip(ptr(qkv), B, N, H, 64, ptr(out), ptr(lse), None, 0, ptr(_skip_check(skip, B, 1)),
+                                  stream())
+    else:
+        lib.ivit_attn_fwd_q2(ptr(qkv), B, N, H, 64, ptr(out), ptr(lse), None, 0, stream())
     if ev is not None:
         ev.record()
     return out, lse
 
 
-def attn_bwd_q2(qkv, out, dout, lse, B, N, H):
+def attn_bwd_q2(qkv, out, dout, lse, B, N, H, skip=None):
+    """skip: as for attn_fwd_q2 — dqkv of a dropped sample is zeros (ivit_attn_bwd_q2_skip)."""
     dqkv = torch.empty_like(qkv)
     ws = workspace(lib.ivit_attn_workspace(BF16, B, N, H, 64, 1), qkv.device)
     ev = KernelTimer.span("attn_bwd")
-    lib.ivit_attn_bwd_q2(ptr(qkv), ptr(out), ptr(dout), ptr(lse), B, N, H, 64, ptr(dqkv), ptr(ws), ws.numel(),
-                         stream())
+    if skip is not None:
+        lib.ivit_attn_bwd_q2_skip(ptr(qkv), ptr(out), ptr(dout), ptr(lse), B, N, H, 64, ptr(dqkv), ptr(ws), ws.numel(),
+                                  ptr(_skip_check(skip, B, 1)), stream())
+    else:
+        lib.ivit_attn_bwd_q2(ptr(qkv), ptr(out), ptr(dout), ptr(lse), B, N, H, 64, ptr(dqkv), ptr(ws), ws.numel(),
+                             stream())
     if ev is not None:
         ev.record()
     return dqkv
@@ -831,21 +881,24 @@ class ViTBlockPanelFn(torch.autograd.Function):
             ln1, m1, r1 = layernorm_fwd(x, n1w, n1b, eps, torch.bfloat16)
         else:
             ln1, m1, r1 = ln_in, m_in, r_in
-        qkv, _ = panel_fwd(ln1, qkvw, qkvb, qcols=H * 64, qscale=Q2_SCALE)
-        o, lse = attn_fwd_q2(qkv, B, N, H)
-        x1, ln2, m2, r2 = linear_resid_ln_fwd(o, pw, pb, x, s1, N, n2w, n2b, eps)
+        # DropPath row skip: s1 / s2 (the branch factors, None without DropPath) also tell each kernel
+        # of a branch which samples are dropped (factor 0): their GEMM panels and attention
+        # workgroups are not computed, and what other kernels still read of them is written as zeros
+        qkv, _ = panel_fwd(ln1, qkvw, qkvb, qcols=H * 64, qscale=Q2_SCALE, skip=s1, rps=N)
+        o, lse = attn_fwd_q2(qkv, B, N, H, skip=s1)
+        x1, ln2, m2, r2 = linear_resid_ln_fwd(o, pw, pb, x, s1, N, n2w, n2b, eps, skip=True)
         # inference (torch.inference_mode): nothing is saved, and fc1 skips its pre-activation copy.
         # training: h = GELU'(fc1 pre-activation) for the fc2 dgrad (panel_dgrad_mul), computed
         # beside GELU from the f32 pre-activation instead of re-evaluated in the backward
         infer = torch.is_inference_mode_enabled()
-        a, h = panel_fwd(ln2, f1w, f1b, act=ACT_GELU if infer else ACT_GELU_D, want_pre=not infer)
+        a, h = panel_fwd(ln2, f1w, f1b, act=ACT_GELU if infer else ACT_GELU_D, want_pre=not infer, skip=s2, rps=N)
         if nxw is not None:
-            x2, lnx, mx, rx = linear_resid_ln_fwd(a, f2w, f2b, x1, s2, N, nxw, nxb, eps)
+            x2, lnx, mx, rx = linear_resid_ln_fwd(a, f2w, f2b, x1, s2, N, nxw, nxb, eps, skip=True)
         else:
             # the last block: the same row-panel residual GEMM (its LayerNorm epilogue on unit
             # parameters, outputs discarded) instead of the 128 x 128 engine's EpiResid GEMM
             g1, b0 = _unit_ln_params(x.shape[1], x.device)
-            x2 = linear_resid_ln_fwd(a, f2w, f2b, x1, s2, N, g1, b0, eps)[0]
+            x2 = linear_resid_ln_fwd(a, f2w, f2b, x1, s2, N, g1, b0, eps, skip=True)[0]
             lnx = mx = rx = x2.new_empty(0)
         ctx.mark_non_differentiable(lnx, mx, rx)
         ctx.set_materialize_grads(False)  # no zero-filled gradients for the three extra outputs
@@ -877,22 +930,23 @@ class ViTBlockPanelFn(torch.autograd.Function):
             hm.g = hm.key = None
         if dx2s is None:
             dx2s = add_act_grad(dx2, row_scale=s2, row_elems=N * x.shape[1], out_dtype=cd)
-        dh = panel_dgrad_mul(dx2s, f2w, h)
+        dh = panel_dgrad_mul(dx2s, f2w, h, skip=s2, rps=N)
         # DDP: the twelve parameter gradients straight into their bucket views (no autograd add)
         direct = grad_sinks(ctx.params)
         dv = direct[1] if direct is not None else [None] * 12
         # fc1 dgrad with norm2's backward in the epilogue
         dx1, dx1s, dg2, dbe2 = linear_dgrad_ln_bwd(dh, f1w, x1, n2w, m2, r2, dres=dx2, dx=torch.empty_like(dx2),
-                                                   xs_dtype=cd, row_scale=s1, rps=N, dg=dv[6], db=dv[7])
-        do = panel_dgrad(dx1s, pw)
-        dqkv = attn_bwd_q2(qkv, o, do, lse, B, N, H)
+                                                   xs_dtype=cd, row_scale=s1, rps=N, dg=dv[6], db=dv[7], skip=s2)
+        do = panel_dgrad(dx1s, pw, skip=s1, rps=N)
+        dqkv = attn_bwd_q2(qkv, o, do, lse, B, N, H, skip=s1)
         # qkv dgrad with norm1's backward in the epilogue
         if hp is not None:  # also the previous block's bf16(dx0 * s2) (GradHandoff)
             dx0, dx0s, dg1, dbe1 = linear_dgrad_ln_bwd(dqkv, qkvw, x, n1w, m1, r1, dres=dx1, dx=dx1, xs_dtype=cd,
-                                                       row_scale=hp.scale, rps=N, dg=dv[0], db=dv[1])
+                                                       row_scale=hp.scale, rps=N, dg=dv[0], db=dv[1], skip=s1)
             hp.g, hp.key = dx0s, GradHandoff.ident(dx0)
         else:
-            dx0, _, dg1, dbe1 = linear_dgrad_ln_bwd(dqkv, qkvw, x, n1w, m1, r1, dres=dx1, dx=dx1, dg=dv[0], db=dv[1])
+            dx0, _, dg1, dbe1 = linear_dgrad_ln_bwd(dqkv, qkvw, x, n1w, m1, r1, dres=dx1, dx=dx1, rps=N, dg=dv[0],
+                                                    db=dv[1], skip=s1)
         # the four weight gradients in one grouped launch after the dgrads (ivit_vit_block_wgrad)
         # instead of four split-K engine GEMMs (-1.5 ms per step, round 3)
         outs = None if direct is None else (dv[10], dv[11], dv[8], dv[9], dv[4], dv[5], dv[2], dv[3])
