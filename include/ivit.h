@@ -503,6 +503,32 @@ int ivit_det_loss_bwd(const float* cls, const float* box, const float* intent, l
                       const float* stats, const float* grad_loss, float* dcls, float* dbox, float* dintent,
                       void* work, long work_bytes, void* stream);
 
+/* ---- Rotated-IoU box regression (no reference code: the reference's box term is Smooth-L1) -- */
+/* Element-wise: iou[i] = IoU_rot(boxes[i], targets[i]) (x, y, w, l, yaw rows, f32; computed in f64
+ * with the conventions and guards of ivit_rotated_iou) and jac[i][0..4] = dIoU/dboxes[i]. A
+ * non-finite coordinate gives NaN. The backward is dboxes[i][k] = grad_iou[i] * jac[i][k].
+ * n = 0 is a no-op.                                                                            */
+int ivit_riou_pairs_fwd(const float* boxes, const float* targets, long n, float* iou, float* jac, void* stream);
+int ivit_riou_pairs_bwd(const float* grad_iou, const float* jac, long n, float* dboxes, void* stream);
+/* The opt-in IoU term of the detection loss: box_loss = (sum SmoothL1 + iou_weight * sum_pos
+ * (1 - IoU_rot(decode(box, anchor), matched GT))) / max(1, num_pos). _fwd runs right after
+ * ivit_det_loss_fwd on the same stream with that call's workspace (det_work, read only: its
+ * leading per-anchor targets name the positives) and stats, which it updates: [12] sum(1 - IoU),
+ * [13] sum IoU, [14] the normalised term (iou_weight included), [15] the positives' mean IoU,
+ * [7] box_loss and [5] loss with the term added; a non-finite new total zeroes [5..8], [14], [15]
+ * and the finite flag [9], and a flag that is already 0 stays 0. use_rotated picks the IoU of the
+ * matched-GT argmax (the assignment's own); the term's IoU is always the rotated one. _bwd runs
+ * right after ivit_det_loss_bwd and adds grad_loss * w_box * iou_weight * (-dIoU/d raw) / max(1,
+ * num_pos) into dbox for the positives (nothing when the finite flag is 0).
+ * work >= ivit_det_iou_loss_workspace(B, NA) bytes, the same buffer in _fwd and _bwd.           */
+long ivit_det_iou_loss_workspace(long B, long NA);
+int ivit_det_iou_loss_fwd(const float* box, const float* anchors, long B, long NA, const float* gt, const int* ngt,
+                          long Gmax, int use_rotated, float w_box, float iou_weight, const void* det_work,
+                          long det_work_bytes, float* stats, void* work, long work_bytes, void* stream);
+int ivit_det_iou_loss_bwd(long B, long NA, float w_box, float iou_weight, const float* stats,
+                          const float* grad_loss, const void* det_work, long det_work_bytes, const void* work,
+                          long work_bytes, float* dbox, void* stream);
+
 /* ---- Geometry (utils.py) ----------------------------------------------------------------- */
 int ivit_generate_anchors(long bev_h, long bev_w, long stride, const float* cfgs, long A, float voxel, float off_x,
                           float off_y, float* out, void* stream);

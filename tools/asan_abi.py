@@ -112,6 +112,24 @@ def driver_source():
               "    ivit_ktime_arm(0);",
               "    calls += 6;",
               "  }",
+              # rotated-IoU entries: positive sizes with NULL pointers, and a workspace one byte short
+              # with real host buffers, are refused before any device call
+              "  {",
+              "    static float buf[64]; static int ib[64];",
+              "    const long need = ivit_det_iou_loss_workspace(1, 8);",
+              "    if (need <= 0 || ivit_det_iou_loss_workspace(0, 8) != 0) return 6;",
+              "    if (ivit_riou_pairs_fwd(nullptr, nullptr, 4, nullptr, nullptr, nullptr) >= 0) return 7;",
+              "    if (ivit_riou_pairs_bwd(nullptr, nullptr, 4, nullptr, nullptr) >= 0) return 8;",
+              "    if (ivit_det_iou_loss_fwd(nullptr, nullptr, 1, 8, nullptr, nullptr, 1, 1, 1.f, 1.f, nullptr, 0, "
+              "nullptr, nullptr, 0, nullptr) >= 0) return 9;",
+              "    if (ivit_det_iou_loss_fwd(buf, buf, 1, 8, buf, ib, 1, 1, 1.f, 1.f, ib, 32, buf, buf, need - 1, "
+              "nullptr) >= 0) return 10;",
+              "    if (ivit_det_iou_loss_bwd(1, 8, 1.f, 1.f, buf, buf, ib, 32, buf, need - 1, buf, nullptr) >= 0) "
+              "return 11;",
+              "    if (ivit_det_iou_loss_bwd(1, 8, 1.f, 1.f, buf, buf, ib, 31, buf, need, buf, nullptr) >= 0) "
+              "return 12;",
+              "    calls += 7;",
+              "  }",
               '  std::printf("asan abi driver: %ld calls, %d failed\\n", calls, failures);',
               "  return failures ? 1 : 0;", "}"]
     return "\n".join(lines) + "\n", len(protos)

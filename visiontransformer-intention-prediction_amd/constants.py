@@ -65,3 +65,7 @@ EVAL_FUSE_BOXES = False  # eval_vit.py --fuse-boxes: kept boxes become the weigh
 
 # train_vit.py / train_cnn.py --clip-grad-norm: global gradient L2-norm bound (None: no clipping, the reference's loop)
 GRAD_CLIP_NORM = None
+
+# train_vit.py / train_cnn.py --iou-loss-weight: weight of the rotated-IoU term (1 - IoU of the decoded box and its
+# matched GT) added to the Smooth-L1 sum of the box loss (0: off, the reference's box term)
+BOX_IOU_LOSS_WEIGHT = 0.0

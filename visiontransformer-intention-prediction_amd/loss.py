@@ -25,6 +25,15 @@ Intention down-sampling (loss.py:169-182), two random streams:
     flattened (sample, anchor) order — so the same torch seed drops the same anchors. It costs an
     assignment pass and a host sync per class (the reference's ``.item()``).
 ``forward(..., intent_keep=mask)`` injects the mask for parity tests.
+
+Rotated-IoU regression (``iou_loss_weight`` λ, 0 = off = the reference's loss bit for bit; no
+reference code behind it): with λ > 0 the box term becomes
+``(Σ_pos Σ_k SmoothL1_k + λ · Σ_pos (1 - IoU_rot(decode(pred), matched GT))) / max(1, num_pos)``.
+Positives and matches are the assignment's own, the decode is ``decode_box_predictions`` in f64
+without the angle wrap, the IoU is always the rotated one. Smooth-L1 stays in the sum: ``1 - IoU``
+has no gradient once a prediction no longer overlaps its target. The dict gains ``iou_loss`` (the
+second summand, normalised) and ``pos_iou`` (the positives' mean IoU); a non-finite decoded box
+fires the same guard, in both forms (the ``sync_guard=True`` message gains an ``IoU:`` figure).
 """
 from __future__ import annotations
 
@@ -35,7 +44,7 @@ import torch
 import torch.nn as nn
 
 import ops
-from constants import DOMINANT_CLASSES_FOR_DOWNSAMPLING, INTENTION_DOWNSAMPLE_RATIO
+from constants import BOX_IOU_LOSS_WEIGHT, DOMINANT_CLASSES_FOR_DOWNSAMPLING, INTENTION_DOWNSAMPLE_RATIO
 
 
 _TLS = threading.local()
@@ -81,8 +90,11 @@ class DetectionIntentionLoss(nn.Module):
                  smooth_l1_beta=1.0 / 9.0, apply_intention_downsampling=True,
                  dominant_intentions=DOMINANT_CLASSES_FOR_DOWNSAMPLING,
                  intention_downsample_ratio=INTENTION_DOWNSAMPLE_RATIO, downsample_rng="device",
-                 sync_guard=None):
+                 sync_guard=None, iou_loss_weight=BOX_IOU_LOSS_WEIGHT):
         super().__init__()
+        if not float(iou_loss_weight) >= 0.0 or float(iou_loss_weight) == float("inf"):
+            raise ValueError(f"iou_loss_weight must be a finite number >= 0, got {iou_loss_weight!r}")
+        self.iou_loss_weight = float(iou_loss_weight)
         if sync_guard not in (None, True, False):
             raise ValueError(f"sync_guard must be None, True or False, got {sync_guard!r}")
         self.sync_guard = sync_guard
@@ -113,7 +125,8 @@ class DetectionIntentionLoss(nn.Module):
                 "class_w": None if cw is None else cw.to(device).float().contiguous(),
                 "pos_thr": self.iou_threshold, "neg_thr": self.neg_iou_threshold, "alpha": self.focal_loss_alpha,
                 "gamma": self.focal_loss_gamma, "beta": self.smooth_l1_beta, "w_cls": self.cls_weight,
-                "w_box": self.box_weight, "w_int": self.intent_weight, "rotated": self.use_rotated_iou}
+                "w_box": self.box_weight, "w_int": self.intent_weight, "rotated": self.use_rotated_iou,
+                "iou_w": self.iou_loss_weight}
 
     def forward(self, cls_logits, box_preds, intention_logits, anchors, gt_list, intent_keep=None):
         B = cls_logits.shape[0]
@@ -134,15 +147,25 @@ class DetectionIntentionLoss(nn.Module):
         cls = cls_logits.float().reshape(B, NA)
         box = box_preds.float().reshape(B, NA, 6)
         it = intention_logits.float().reshape(B, NA, -1)
-        loss, stats = ops.DetLossFn.apply(cls, box, it, anchors, gt, ng, gi, keep, self._cfg(dev))
+        fn = ops.DetIouLossFn if self.iou_loss_weight > 0 else ops.DetLossFn
+        loss, stats = fn.apply(cls, box, it, anchors, gt, ng, gi, keep, self._cfg(dev))
         # 1.0 / 0.0 on device: 0 means the guard of loss.py:190-198 fired (loss and terms are 0,
         # and the backward writes exact zero gradients); trainer.Trainer skips the update on it
         self.last_finite = stats[9].detach()
         sync = self.sync_guard if self.sync_guard is not None else not getattr(_TLS, "device", False)
         if sync:
             return self._reference_guard(loss, stats, dev)
-        return {"loss": loss, "cls_loss": stats[6].detach(), "box_loss": stats[7].detach(),
-                "intent_loss": stats[8].detach(), "num_pos_anchors": stats[3].detach().round().long()}
+        return self._with_iou({"loss": loss, "cls_loss": stats[6].detach(), "box_loss": stats[7].detach(),
+                               "intent_loss": stats[8].detach(),
+                               "num_pos_anchors": stats[3].detach().round().long()}, stats)
+
+    def _with_iou(self, d, stats):
+        """The two extra entries of the rotated-IoU term (iou_loss_weight > 0): ``iou_loss``, the
+        term's share of box_loss (weight included, normalised by the positives), and ``pos_iou``,
+        the positives' mean IoU; both 0 with no positives or when the guard fired."""
+        if self.iou_loss_weight > 0:
+            d["iou_loss"], d["pos_iou"] = stats[14].detach(), stats[15].detach()
+        return d
 
     def _reference_guard(self, loss, stats, dev):
         """loss.py:190-206 with one host read of (finite flag, positive count, raw terms)."""
@@ -155,12 +178,21 @@ class DetectionIntentionLoss(nn.Module):
             cl = float(h[0]) / cden
             bl = float(h[1]) / cden if num_pos > 0 else 0.0
             il = float(h[2]) / iden if num_pos > 0 else 0.0
-            print(f"NaN or Inf DETECTED IN LOSS! Cls: {cl}, Box: {bl}, Intent: {il}")
+            iou = ""
+            if self.iou_loss_weight > 0:
+                # the raw IoU term (slot 12: sum of 1 - IoU over the positives), part of Box
+                ul = self.iou_loss_weight * float(h[12]) / cden if num_pos > 0 else 0.0
+                bl += ul
+                iou = f", IoU: {ul}"
+            print(f"NaN or Inf DETECTED IN LOSS! Cls: {cl}, Box: {bl}, Intent: {il}{iou}")
             z = torch.tensor(0.0, device=dev)
-            return {"loss": torch.tensor(0.0, device=dev, requires_grad=True), "cls_loss": z,
-                    "box_loss": z.clone(), "intent_loss": z.clone(), "num_pos_anchors": num_pos}
-        return {"loss": loss, "cls_loss": stats[6].detach(), "box_loss": stats[7].detach(),
-                "intent_loss": stats[8].detach(), "num_pos_anchors": num_pos}
+            d = {"loss": torch.tensor(0.0, device=dev, requires_grad=True), "cls_loss": z,
+                 "box_loss": z.clone(), "intent_loss": z.clone(), "num_pos_anchors": num_pos}
+            if self.iou_loss_weight > 0:
+                d["iou_loss"], d["pos_iou"] = z.clone(), z.clone()
+            return d
+        return self._with_iou({"loss": loss, "cls_loss": stats[6].detach(), "box_loss": stats[7].detach(),
+                               "intent_loss": stats[8].detach(), "num_pos_anchors": num_pos}, stats)
 
     def _reference_keep(self, cls_logits, box_preds, intention_logits, anchors, gt, ng, gi):
         """The keep mask of the reference's draws (loss.py:170-178): the per-anchor targets from one

@@ -12,6 +12,8 @@ Granularity (fused for HBM traffic and launch count, coarse enough for DDP overl
   * ``NeckFn``        final norms + adapters + fusion BasicBlocks + heads
                       (model_vit.py:116-142, 179-185; heads.py)
   * ``DetLossFn``     DetectionIntentionLoss                        (loss.py:58-206)
+  * ``DetIouLossFn`` / ``RotatedIouPairsFn``  the same loss with the opt-in rotated-IoU regression
+                      term, and the element-wise differentiable rotated IoU (no reference code)
   * ``TokenSelectFn`` / ``PredLinearFn`` / ``MaeLossFn``  the token gather / un-shuffle, prediction
                       head and reconstruction loss of MAE pre-training (mae.py; no reference code)
 plus single-op Functions used by the standalone module forwards.
@@ -1245,6 +1247,97 @@ class DetLossFn(torch.autograd.Function):
                               cfg["beta"], cfg["w_cls"], cfg["w_box"], cfg["w_int"], ptr(stats), ptr(g), ptr(dcls),
                               ptr(dbox), ptr(dint), ptr(ws), ws.numel(), stream())
         return dcls, dbox, dint, None, None, None, None, None, None
+
+
+class DetIouLossFn(torch.autograd.Function):
+    """DetLossFn with the rotated-IoU regression term (cfg["iou_w"] > 0): ivit_det_loss_fwd then
+    ivit_det_iou_loss_fwd on the same stream, one loss scalar; the backward runs ivit_det_loss_bwd
+    then ivit_det_iou_loss_bwd, which adds the term's gradient into dbox. stats[12..15]: sum(1 - IoU),
+    sum IoU, the normalised term, the positives' mean IoU; stats[9] is the combined finite flag."""
+
+    @staticmethod
+    def forward(ctx, cls, box, intent, anchors, gt, ngt, gint, keep, cfg):
+        B, NA = cls.shape[0], cls.shape[1]
+        K = intent.shape[-1]
+        G = gt.shape[1]
+        dev = cls.device
+        stats = torch.zeros((16,), dtype=torch.float32, device=dev)
+        ws = workspace(lib.ivit_det_loss_workspace(B, NA, G), dev)
+        iws = workspace(lib.ivit_det_iou_loss_workspace(B, NA), dev)
+        cls, box, intent = cls.contiguous(), box.contiguous(), intent.contiguous()
+        lib.ivit_det_loss_fwd(ptr(cls), ptr(box), ptr(intent), ptr(anchors), B, NA, K, ptr(gt), ptr(ngt), ptr(gint), G,
+                              ptr(keep), cfg["dominant_mask"], int(cfg["downsampling"]), ptr(cfg.get("class_w")),
+                              cfg["pos_thr"], cfg["neg_thr"], cfg["alpha"], cfg["gamma"], cfg["beta"], cfg["w_cls"],
+                              cfg["w_box"], cfg["w_int"], int(cfg["rotated"]), ptr(stats), ptr(ws), ws.numel(),
+                              stream())
+        lib.ivit_det_iou_loss_fwd(ptr(box), ptr(anchors), B, NA, ptr(gt), ptr(ngt), G, int(cfg["rotated"]),
+                                  cfg["w_box"], cfg["iou_w"], ptr(ws), ws.numel(), ptr(stats), ptr(iws), iws.numel(),
+                                  stream())
+        ctx.save_for_backward(cls, box, intent, keep, stats, ws, iws)
+        ctx.cfg = cfg
+        ctx.shape = (B, NA, K)
+        ctx.mark_non_differentiable(stats)
+        ctx.set_materialize_grads(False)
+        loss = stats[5:6].clone().reshape(())
+        return loss, stats
+
+    @staticmethod
+    def backward(ctx, gloss, _gstats):
+        cls, box, intent, keep, stats, ws, iws = ctx.saved_tensors
+        B, NA, K = ctx.shape
+        cfg = ctx.cfg
+        if gloss is None:
+            return None, None, None, None, None, None, None, None, None
+        g = gloss.reshape(1).float().contiguous()
+        dcls, dbox, dint = torch.empty_like(cls), torch.empty_like(box), torch.empty_like(intent)
+        lib.ivit_det_loss_bwd(ptr(cls), ptr(box), ptr(intent), B, NA, K, ptr(keep), cfg["dominant_mask"],
+                              int(cfg["downsampling"]), ptr(cfg.get("class_w")), cfg["alpha"], cfg["gamma"],
+                              cfg["beta"], cfg["w_cls"], cfg["w_box"], cfg["w_int"], ptr(stats), ptr(g), ptr(dcls),
+                              ptr(dbox), ptr(dint), ptr(ws), ws.numel(), stream())
+        lib.ivit_det_iou_loss_bwd(B, NA, cfg["w_box"], cfg["iou_w"], ptr(stats), ptr(g), ptr(ws), ws.numel(),
+                                  ptr(iws), iws.numel(), ptr(dbox), stream())
+        return dcls, dbox, dint, None, None, None, None, None, None
+
+
+class RotatedIouPairsFn(torch.autograd.Function):
+    """iou[i] = IoU_rot(boxes[i], targets[i]), differentiable in boxes: the forward writes the n x 5
+    Jacobian (ivit_riou_pairs_fwd), the backward scales it (ivit_riou_pairs_bwd)."""
+
+    @staticmethod
+    def forward(ctx, boxes, targets):
+        n = boxes.shape[0]
+        iou = torch.empty((n,), dtype=torch.float32, device=boxes.device)
+        jac = torch.empty((n, 5), dtype=torch.float32, device=boxes.device)
+        if n:
+            lib.ivit_riou_pairs_fwd(ptr(boxes), ptr(targets), n, ptr(iou), ptr(jac), stream())
+        ctx.save_for_backward(jac)
+        return iou
+
+    @staticmethod
+    def backward(ctx, giou):
+        (jac,) = ctx.saved_tensors
+        n = jac.shape[0]
+        dboxes = torch.empty_like(jac)
+        if n:
+            giou = giou.float().contiguous()
+            lib.ivit_riou_pairs_bwd(ptr(giou), ptr(jac), n, ptr(dboxes), stream())
+        return dboxes, None
+
+
+def rotated_iou_pairs(boxes, targets):
+    """Rotated IoU of the box pairs (boxes[i], targets[i]) -> f32 (n,), differentiable with respect to
+    ``boxes`` (x, y, w, l, yaw; f32 (n, 5) device tensors). The conventions and guards are those of
+    utils.compute_rotated_iou: degenerate or disjoint pairs give 0 with a zero gradient; a non-finite
+    coordinate gives NaN. n = 0 returns empty tensors and launches nothing."""
+    for name, t in (("boxes", boxes), ("targets", targets)):
+        if not t.is_cuda:
+            raise RuntimeError(f"ops.rotated_iou_pairs: {name} must be a device tensor (no CPU fallback)")
+        if t.dim() != 2 or t.shape[1] != 5 or t.dtype != torch.float32:
+            raise ValueError(f"ops.rotated_iou_pairs: {name} must be f32 (n, 5), got {t.dtype} {tuple(t.shape)}")
+    if boxes.shape[0] != targets.shape[0] or boxes.device != targets.device:
+        raise ValueError(f"ops.rotated_iou_pairs: {boxes.shape[0]} boxes on {boxes.device} for "
+                         f"{targets.shape[0]} targets on {targets.device}")
+    return RotatedIouPairsFn.apply(boxes.contiguous(), targets.detach().contiguous())
 
 
 # ------------------------------------------------------------------------------ MAE pre-training

@@ -44,8 +44,9 @@ from pathlib import Path
 
 import torch
 
-from constants import (ANCHOR_CONFIGS_PAPER, DOMINANT_CLASSES_FOR_DOWNSAMPLING, GRAD_CLIP_NORM, GRID_HEIGHT_PX,
-                       GRID_WIDTH_PX, INTENTION_DOWNSAMPLE_RATIO, LIDAR_SWEEPS, LIDAR_TOTAL_CHANNELS, MAP_CHANNELS)
+from constants import (ANCHOR_CONFIGS_PAPER, BOX_IOU_LOSS_WEIGHT, DOMINANT_CLASSES_FOR_DOWNSAMPLING, GRAD_CLIP_NORM,
+                       GRID_HEIGHT_PX, GRID_WIDTH_PX, INTENTION_DOWNSAMPLE_RATIO, LIDAR_SWEEPS, LIDAR_TOTAL_CHANNELS,
+                       MAP_CHANNELS)
 from ddp import all_reduce_sum, any_rank, init_distributed
 from loss import DetectionIntentionLoss
 from model_vit import BasicBlock, IntentNetViT
@@ -122,6 +123,9 @@ def parse_args(argv=None):
     ap.add_argument("--clip-grad-norm", type=float, default=GRAD_CLIP_NORM, metavar="X",
                     help="clip the global gradient L2 norm to X on the device (no host sync); a non-finite "
                          "gradient norm skips the update")
+    ap.add_argument("--iou-loss-weight", type=float, default=BOX_IOU_LOSS_WEIGHT, metavar="X",
+                    help="add X * (1 - rotated IoU of the decoded box and its matched GT) per positive anchor to the "
+                         "Smooth-L1 sum of the box loss (0: off)")
     ap.add_argument("--ema-decay", type=float, default=None, metavar="D",
                     help="keep an exponential moving average of the weights with decay D in [0, 1) (updated in the "
                          "optimiser's launch) and save it as 'ema_state_dict'")
@@ -148,6 +152,8 @@ def parse_args(argv=None):
     ap.add_argument("--warmup-epochs", type=float, default=0.0, metavar="E", help="with --sched cosine")
     ap.add_argument("--min-lr", type=float, default=0.0, metavar="X", help="with --sched cosine")
     args = ap.parse_args(argv)
+    if not 0.0 <= args.iou_loss_weight < float("inf"):
+        ap.error(f"--iou-loss-weight {args.iou_loss_weight}: must be a finite number >= 0")
     if args.layer_decay is not None and not 0.0 < args.layer_decay <= 1.0:
         ap.error(f"--layer-decay {args.layer_decay}: must be in (0, 1]")
     if args.sched == "cosine":
@@ -296,7 +302,10 @@ def main(argv=None, variant="vit"):
     loss_fn = DetectionIntentionLoss(use_rotated_iou=USE_ROTATED_IOU, intention_class_weights=None,
                                      apply_intention_downsampling=APPLY_INTENTION_DOWNSAMPLING,
                                      dominant_intentions=DOMINANT_CLASSES_FOR_DOWNSAMPLING,
-                                     intention_downsample_ratio=INTENTION_DOWNSAMPLE_RATIO).to(device)
+                                     intention_downsample_ratio=INTENTION_DOWNSAMPLE_RATIO,
+                                     iou_loss_weight=args.iou_loss_weight).to(device)
+    if args.iou_loss_weight > 0:
+        log(f"Box loss: Smooth-L1 + {args.iou_loss_weight:g} x (1 - rotated IoU) per positive anchor")
     optimizer = build_optimizer(model, args, log)
     # every rank's loader has the same length in lockstep mode or a shorter one ends the epoch for all:
     # the schedule then simply reaches fewer updates than it spans
@@ -319,7 +328,8 @@ def main(argv=None, variant="vit"):
     log(f"\n--- Starting {tag} Training ---")
     for epoch in range(args.epochs):
         model.train()
-        acc = torch.zeros(4, dtype=torch.float64, device=device)
+        iou_on = args.iou_loss_weight > 0
+        acc = torch.zeros(6 if iou_on else 4, dtype=torch.float64, device=device)
         n_ok = 0
         t0 = time.perf_counter()
         for batch_idx, batch in enumerate(_in_lockstep(loader, device) if not args.synthetic else loader):
@@ -329,18 +339,22 @@ def main(argv=None, variant="vit"):
             if d is None:
                 log(f"Warning: NaN detected at batch {batch_idx + 1}. Skipping batch.")
                 continue
-            acc += torch.stack([d["loss"].detach(), d["cls_loss"], d["box_loss"], d["intent_loss"]]).double()
+            terms = [d["loss"].detach(), d["cls_loss"], d["box_loss"], d["intent_loss"]]
+            if iou_on:
+                terms += [d["iou_loss"], d["pos_iou"]]
+            acc += torch.stack(terms).double()
             n_ok += 1
         torch.cuda.synchronize()
         dt = time.perf_counter() - t0
         # global epoch mean over ranks: every rank steps ReduceLROnPlateau on the same value, so
         # the LR (and with it the all-reduced update) stays identical across replicas
         tot = all_reduce_sum(acc.tolist() + [n_ok], device)
-        acc, n_ok = torch.tensor(tot[:4], dtype=torch.float64), int(round(tot[4]))
+        acc, n_ok = torch.tensor(tot[:-1], dtype=torch.float64), int(round(tot[-1]))
         if n_ok > 0:
             avg = (acc / n_ok).tolist()
+            iou_terms = f", iou_loss: {avg[4]:.4f}, pos_iou: {avg[5]:.4f}" if iou_on else ""
             log(f"Epoch {epoch + 1} Summary: Avg Loss: {avg[0]:.4f} (Cls: {avg[1]:.4f}, Box: {avg[2]:.4f}, "
-                f"Intent: {avg[3]:.4f}) LR: {optimizer.param_groups[0]['lr']:{'.1e' if lr_sched is None else '.3e'}}  "
+                f"Intent: {avg[3]:.4f}{iou_terms}) LR: {optimizer.param_groups[0]['lr']:{'.1e' if lr_sched is None else '.3e'}}  "
                 f"[{n_ok * args.batch / dt:.1f} samples/s]")
             if args.clip_grad_norm is not None:
                 log(grad_clip_line(trainer.grad_stats(), args.clip_grad_norm))
