@@ -488,8 +488,15 @@ int ivit_grad_scale(long n_tensors, void* const* grads, const long* sizes, const
 /* ---- Detection / intention loss (loss.py:58-206): assignment + focal + Smooth-L1 + CE. ----- */
 /* gt: [B, Gmax, 5] f32 padded, ngt[B] int32, gint[B, Gmax] int32. keep: [B, NA] f32 0/1 (dominant
  * intent keep mask) or null. stats (f32[8]): focal_sum, box_sum, ce_sum, num_pos, keep_sum, loss,
- * cls_loss, box_loss, intent_loss (written). The workspace starts with the per-anchor targets,
- * int32 [B, NA]: (cls target + 1) | (intent target + 1) << 2 (cls -1 = ignored, intent -1 = none). */
+ * cls_loss, box_loss, intent_loss (written), then [9] the finite flag, [10] max(1, num_pos), [11] the
+ * intention term's denominator.
+ * Workspace contract (callers may read it after _fwd; _bwd and ivit_det_iou_loss_* do): it starts with
+ * the per-anchor targets, at offsets that do not depend on Gmax:
+ *   tgt   int32 [B * NA] at byte 0: (cls target + 1) in bits 0-1 (cls -1 = ignored, 0 = negative,
+ *         1 = positive), (intent target + 1) << 2 above (intent -1 = none: every non-positive anchor);
+ *   box_t f32 [B * NA * 6] at the next 256-byte boundary after tgt, (B * NA * 4 + 255) / 256 * 256: the
+ *         six delta targets of the matched GT; only the rows of positive anchors are written.
+ * What follows them (per-block partial sums, best anchor per GT) is private to the kernels.         */
 long ivit_det_loss_workspace(long B, long NA, long Gmax);
 int ivit_det_loss_fwd(const float* cls, const float* box, const float* intent, const float* anchors, long B,
                       long NA, long K, const float* gt, const int* ngt, const int* gint, long Gmax,

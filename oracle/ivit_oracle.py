@@ -366,18 +366,19 @@ def assign_targets(anchors, gt_list, pos_thr=0.6, neg_thr=0.45, iou_fn=axis_alig
 
 def detection_loss(cls_logits, box_preds, intent_logits, anchors, gt_list, *, downsampling=True,
                    keep=None, keep_prob=0.15, dominant=DOMINANT, class_weights=None, alpha=0.25, gamma=2.0,
-                   beta=1.0 / 9.0, w_cls=1.0, w_box=1.0, w_int=0.5, iou_fn=axis_aligned_iou):
+                   beta=1.0 / 9.0, w_cls=1.0, w_box=1.0, w_int=0.5, iou_fn=axis_aligned_iou, pos_thr=0.6,
+                   neg_thr=0.45):
     """loss.py:58-206. ``keep``: optional (B, NA) float 0/1 per-anchor keep mask applied to
     dominant-class positives (the product's device-RNG formulation); ``None`` reproduces
     the reference's global-RNG ``torch.rand`` draws in dominant-class order."""
-    cls_t, box_t, int_t = assign_targets(anchors, gt_list, iou_fn=iou_fn)
+    cls_t, box_t, int_t = assign_targets(anchors, gt_list, pos_thr=pos_thr, neg_thr=neg_thr, iou_fn=iou_fn)
     ct, bt, it = cls_t.reshape(-1), box_t.reshape(-1, 6), int_t.reshape(-1)
     cl = cls_logits.reshape(-1, 1)
     valid, pos = ct >= 0, ct == 1
     num_pos = pos.sum()
     cls_loss = torch.tensor(0.0)
     if valid.any():
-        cls_loss = sigmoid_focal_loss(cl[valid], ct[valid].float().unsqueeze(1), alpha, gamma).sum() / max(1, num_pos)
+        cls_loss = sigmoid_focal_loss(cl[valid], ct[valid].to(cl.dtype).unsqueeze(1), alpha, gamma).sum() / max(1, num_pos)
     box_loss = torch.tensor(0.0)
     int_loss = torch.tensor(0.0)
     if num_pos > 0:

@@ -74,7 +74,14 @@ IVIT_DEV float focal_grad(float x, float t, float alpha, float gamma) {
   const float ce = fmaxf(x, 0.f) - x * t + log1pf(expf(-fabsf(x)));
   const float pt = p * t + (1.f - p) * (1.f - t);
   const float omp = 1.f - pt;
-  float g = (p - t) * powf(omp, gamma) - ce * gamma * powf(omp, gamma - 1.f) * (2.f * t - 1.f) * p * (1.f - p);
+  float g;
+  if (gamma >= 1.f) {
+    g = (p - t) * powf(omp, gamma) - ce * gamma * powf(omp, gamma - 1.f) * (2.f * t - 1.f) * p * (1.f - p);
+  } else {
+    // omp rounds to 0 for a confident correct logit, and omp^(gamma-1) is then inf (0 * inf = NaN at
+    // gamma = 0). For t in {0, 1}, p (1 - p) / omp = pt, so omp^gamma factors out and nothing diverges.
+    g = powf(omp, gamma) * ((p - t) - ce * gamma * (2.f * t - 1.f) * pt);
+  }
   if (alpha >= 0.f) g *= alpha * t + (1.f - alpha) * (1.f - t);
   return g;
 }
