@@ -536,7 +536,22 @@ int ivit_det_iou_loss_bwd(long B, long NA, float w_box, float iou_weight, const 
                           const float* grad_loss, const void* det_work, long det_work_bytes, const void* work,
                           long work_bytes, float* dbox, void* stream);
 
-/* ---- Geometry (utils.py) ----------------------------------------------------------------- */
+/* ---- Geometry (utils.py) -----------------------------------------------------------------
+ * ivit_generate_anchors: out [fh*fw*A, 5] with fh = bev_h / stride, fw = bev_w / stride (floor),
+ * rows location-major, anchor-minor; bit-equal to the reference's f32 arithmetic. No rows (a side
+ * shorter than the stride, A = 0): returns 0 and writes nothing.
+ * ivit_axis_iou / ivit_rotated_iou: out [n1, n2] row-major, out[r * n2 + c] = IoU(b1[r], b2[c]) of
+ * xywha rows (the axis form reads columns 0..3). Every element of the output is written; n1 = 0 or
+ * n2 = 0 returns 0 and writes nothing. Axis: inputs without a NaN follow the reference
+ * (compute_axis_aligned_iou in f32, its operation order) bit for bit, zero, negative and infinite
+ * sizes included (where that arithmetic gives NaN, so does this); the value for a box with a NaN
+ * field is unspecified (fmaxf / fminf drop a NaN that torch.maximum propagates). Rotated: the f64
+ * convex clip rounded once to f32, within 2^-24 |iou| + 1e-9 of the exact value for areas >= 0.1
+ * and coordinates that f64 resolves to 1e-9 of the box size; an area below 1e-6, an intersection
+ * of at most 1e-7 or a union of at most 1e-6 gives exactly 0.
+ * ivit_decode_boxes: out[i] = decode(rel[i], anchors[idx ? idx[i] : i]); idx (int64, any order,
+ * repeats allowed) gathers from a longer anchor table and gives the bits of the call without it
+ * on the gathered rows. The decoded yaw lies in [-pi, pi].                                       */
 int ivit_generate_anchors(long bev_h, long bev_w, long stride, const float* cfgs, long A, float voxel, float off_x,
                           float off_y, float* out, void* stream);
 int ivit_axis_iou(const float* b1, long n1, const float* b2, long n2, float* out, void* stream);

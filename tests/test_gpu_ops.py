@@ -933,8 +933,10 @@ def test_geometry_golden():
     np.testing.assert_allclose(r.cpu().numpy(), z["rot_iou"], atol=1e-6)
     gt0 = torch.from_numpy(z["gt0_boxes"]).to(DEV)
     iou = utils.compute_axis_aligned_iou(a, gt0)
-    mx, arg = iou.max(dim=1)
-    assert np.array_equal(mx.cpu().numpy(), z["iou_max"])
+    mx, arg = iou.cpu().max(dim=1)  # the argmax on the host, where ties go to the first index as in the golden run
+    assert np.array_equal(mx.numpy(), z["iou_max"]) and np.array_equal(arg.numpy(), z["iou_arg"])
+    assert np.array_equal(iou.cpu().max(dim=0)[1].numpy(), z["iou_arg0"])
+    assert np.array_equal(iou.cpu().numpy()[::97], z["iou_sample"])
 
 
 def test_nms_bitexact_golden():

@@ -1,10 +1,20 @@
 // Box geometry device functions shared by the loss and the eval kernels (utils.py).
 // Bit-exactness with the reference's f32 tensor arithmetic requires no FMA contraction:
 // every file including this header compiles with `#pragma clang fp contract(off)`.
+//
+// hipcc compiles the header as device code for the library; any C++17 compiler takes it as plain
+// host code (tools/geom_host.cpp), so the clip runs under host sanitizers, as geom_ad.h does.
 #pragma once
+#if defined(__HIPCC__)
 #include "ivit_common.h"
+#else
+#include <math.h>
+#define IVIT_DEV inline
+#endif
 
+#if defined(__clang__)
 #pragma clang fp contract(off)
+#endif
 
 namespace ivit {
 
@@ -39,11 +49,15 @@ IVIT_DEV void rect_poly(const float* b, Poly& p) {
   }
 }
 
+// Shoelace sum about the first vertex (p.n >= 1): the products are of the size of the polygon, not
+// of its distance from the origin. Taken about the origin, a 1 m^2 box at |x|, |y| ~ 1e4 m lost
+// 1e-8 m^2 to the cancellation of products near 1e8.
 IVIT_DEV double poly_area_signed(const Poly& p) {
+  const double x0 = p.x[0], y0 = p.y[0];
   double s = 0.0;
   for (int i = 0; i < p.n; ++i) {
     const int j = (i + 1) % p.n;
-    s += p.x[i] * p.y[j] - p.y[i] * p.x[j];
+    s += (p.x[i] - x0) * (p.y[j] - y0) - (p.y[i] - y0) * (p.x[j] - x0);
   }
   return 0.5 * s;
 }
