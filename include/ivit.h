@@ -292,6 +292,29 @@ int ivit_attn_fwd_q2_skip(const void* qkv, long B, long N, long H, long Dh, void
 int ivit_attn_bwd_q2_skip(const void* qkv, const void* out, const void* dout, const float* lse, long B, long N,
                           long H, long Dh, void* dqkv, void* work, long work_bytes, const float* skip, void* stream);
 
+/* ---- Windowed attention (ViTDet, Li et al. 2022; no reference counterpart): the same operands as the
+ *      global entries above, N = 1 + gh*gw tokens: token 0 is CLS, patch token 1 + r*gw + c sits at
+ *      (r, c) of the gh x gw grid. Windows of (wh, ww) patches tile the grid from its top-left corner,
+ *      the last row / column of windows smaller when the size does not divide the grid (no padding, no
+ *      wrap). A patch query attends to the patch keys of its own window only; CLS is a window of its
+ *      own (o_cls = v_cls, its lse its single score). wh * ww <= 256; a window larger than the grid is
+ *      the grid. One workgroup per (window, sample, head) holds the window in LDS: no workspace, no
+ *      atomics, bitwise repeatable. lse [B, H, N] f32 in the units of the global entry of the same
+ *      name (natural log; log2 for _q2). The backward entries read neither out nor lse (rows are
+ *      renormalised by their own sum). _q2: bf16 with the Q block prescaled by log2(e)/sqrt(Dh), dqkv
+ *      w.r.t. the UNSCALED q, k, v; skip as for ivit_attn_fwd_q2_skip (null: none; zeros for a sample
+ *      with factor 0, its lse unwritten; IVIT_KNOB_DROP_SKIP at 0 ignores it). IVIT_ERR_ARG, with
+ *      nothing launched, for Dh != 64, wh or ww < 1, wh * ww > 256, N != 1 + gh*gw and
+ *      N * B * H > 2^31 - 1 (the launch is one flat grid, at most one workgroup per token and head). */
+int ivit_attn_win_fwd(int dtype, const void* qkv, long B, long N, long gh, long gw, long wh, long ww, long H, long Dh,
+                      void* out, float* lse, void* stream);
+int ivit_attn_win_bwd(int dtype, const void* qkv, const void* out, const void* dout, const float* lse, long B, long N,
+                      long gh, long gw, long wh, long ww, long H, long Dh, void* dqkv, void* stream);
+int ivit_attn_win_fwd_q2(const void* qkv, long B, long N, long gh, long gw, long wh, long ww, long H, long Dh,
+                         void* out, float* lse, const float* skip, void* stream);
+int ivit_attn_win_bwd_q2(const void* qkv, const void* out, const void* dout, const float* lse, long B, long N, long gh,
+                         long gw, long wh, long ww, long H, long Dh, void* dqkv, const float* skip, void* stream);
+
 /* ---- Attention probabilities of chosen query rows (model_vit.py:64,71 -> timm Attention: the rows
  *      softmax(q k^T / sqrt(Dh)) that a forward hook on timm's attention would read; the reference
  *      lists their qualitative analysis as future work). qkv as for ivit_attn_fwd: [B, N, 3, H, Dh]

@@ -128,7 +128,11 @@ def parse_args(argv=None):
     ap.add_argument("--regrid", action="store_true",
                     help="build the model at --grid instead of the checkpoint's img_size and resample the streams' "
                          "pos_embed onto it (ViT only)")
-    return ap.parse_args(argv)
+    from train_vit import add_window_args, window_args
+    add_window_args(ap)
+    args = ap.parse_args(argv)
+    args.window_size, args.global_attn_indexes = window_args(ap, args, blocks_alone=True)
+    return args
 
 
 class AttnDump:
@@ -216,6 +220,8 @@ def main_eval_vit(argv=None, variant="vit"):
         raise SystemExit("--attn-maps: IntentNetCNN has no attention to map (use eval_vit.py)")
     if args.regrid and variant != "vit":
         raise SystemExit("--regrid: IntentNetCNN has no position embedding tied to a grid (use eval_vit.py)")
+    if args.window_size is not None and variant != "vit":
+        raise SystemExit("--window: IntentNetCNN has no attention to window (use eval_vit.py)")
     if args.checkpoint is None:
         args.checkpoint = MODEL_SAVE_PATH_VIT if variant == "vit" else MODEL_SAVE_PATH_CNN
     if not torch.cuda.is_available():
@@ -246,10 +252,22 @@ def main_eval_vit(argv=None, variant="vit"):
         return 1
     if variant == "vit":
         cfg = default_cfg(dict(cfg), (H, W))
+        # the flags override what the checkpoint says: --window its window (the global blocks then follow
+        # --global-blocks, or the default rule), --global-blocks alone the global blocks of its window
+        if args.window_size is not None:
+            cfg['vit_window_size'] = args.window_size
+            cfg['vit_global_attn_indexes'] = args.global_attn_indexes
+        elif args.global_attn_indexes is not None:
+            if cfg.get('vit_window_size') is None:
+                raise SystemExit("--global-blocks: the checkpoint has no window to keep blocks out of (add --window)")
+            cfg['vit_global_attn_indexes'] = args.global_attn_indexes
         src_img_size = tuple(cfg['img_size'])
         if args.regrid:
             cfg['img_size'] = (H, W)
         model = IntentNetViT(backbone_cfg=cfg).to(device)
+        if cfg.get('vit_window_size') is not None:
+            from train_vit import window_line
+            print(window_line(model))
         img_size = tuple(cfg['img_size'])
     else:
         from model_cnn import IntentNetCNN

@@ -94,6 +94,10 @@ class MaskedAutoencoderViT(nn.Module):
                              f"kernels take a head dim of 64")
         if any(b.drop_path_rate > 0.0 for b in encoder.blocks):
             raise ValueError("MaskedAutoencoderViT: build the encoder with drop_path_rate=0 (create_mae does)")
+        if any(b.window_size is not None for b in encoder.blocks):
+            # the encoder runs on a gathered subset of the tokens: a spatial window has no meaning there
+            raise ValueError("MaskedAutoencoderViT: the encoder has windowed-attention blocks "
+                             f"{encoder.windowed_blocks()}; pre-train with window_size=None")
         self.encoder = encoder
         pe = encoder.patch_embed
         self.patch = pe.patch_size[0]

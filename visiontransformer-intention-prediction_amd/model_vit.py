@@ -60,12 +60,18 @@ class TwoStreamViTBackbone(nn.Module):
                  drop_path_rate_lidar=0.1, drop_path_rate_map=0.1, lidar_adapter_out_channels=192,
                  map_adapter_out_channels=192, fusion_block_planes=512, fusion_block_layers=2,
                  fusion_block_kernel_size=3, fusion_block_stride=1, res_block_type=BasicBlock,
-                 pretrained_lidar_file=None, pretrained_map_file=None):
+                 pretrained_lidar_file=None, pretrained_map_file=None, vit_window_size=None,
+                 vit_global_attn_indexes=None):
         """The reference's arguments (model_vit.py:38-47). ``pretrained_lidar`` / ``pretrained_map``
         load timm weights of the stream's architecture from a local file (vit.create_model:
         $IVIT_PRETRAINED_DIR/<name>.safetensors|.pth|.bin); ``pretrained_lidar_file`` /
-        ``pretrained_map_file`` name the file directly and imply pretrained for that stream."""
+        ``pretrained_map_file`` name the file directly and imply pretrained for that stream.
+        ``vit_window_size``: (wh, ww) for windowed attention in both streams (None: global in every
+        block); ``vit_global_attn_indexes``: the blocks that stay global (None: ViTDet's rule,
+        vit.default_global_attn_indexes). Neither changes a state_dict key."""
         super().__init__()
+        win = dict(window_size=None if vit_window_size is None else tuple(vit_window_size),
+                   global_attn_indexes=None if vit_global_attn_indexes is None else tuple(vit_global_attn_indexes))
         self.img_size = tuple(img_size)
         self.lidar_adapter_out_channels = lidar_adapter_out_channels
         self.map_adapter_out_channels = map_adapter_out_channels
@@ -73,14 +79,16 @@ class TwoStreamViTBackbone(nn.Module):
         over_m = {"file": pretrained_map_file} if pretrained_map_file is not None else None
         self.vit_lidar = timm_like.create_model(vit_model_name_lidar, pretrained=bool(pretrained_lidar or over_l),
                                                 in_chans=lidar_input_channels, img_size=self.img_size,
-                                                drop_path_rate=drop_path_rate_lidar, pretrained_cfg_overlay=over_l)
+                                                drop_path_rate=drop_path_rate_lidar, pretrained_cfg_overlay=over_l,
+                                                **win)
         self.vit_lidar.head = nn.Identity()
         self.lidar_embed_dim = self.vit_lidar.embed_dim
         self.lidar_num_prefix_tokens = self.vit_lidar.num_prefix_tokens
         self.lidar_grid_size = tuple(self.vit_lidar.patch_embed.grid_size)
         self.vit_map = timm_like.create_model(vit_model_name_map, pretrained=bool(pretrained_map or over_m),
                                               in_chans=map_input_channels, img_size=self.img_size,
-                                              drop_path_rate=drop_path_rate_map, pretrained_cfg_overlay=over_m)
+                                              drop_path_rate=drop_path_rate_map, pretrained_cfg_overlay=over_m,
+                                              **win)
         self.vit_map.head = nn.Identity()
         self.map_embed_dim = self.vit_map.embed_dim
         self.map_num_prefix_tokens = self.vit_map.num_prefix_tokens

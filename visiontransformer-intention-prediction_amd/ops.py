@@ -522,6 +522,82 @@ def attn_bwd(qkv, out, dout, lse, B, N, H, cdt):
     return dqkv
 
 
+def _win_check(qkv, B, N, H, win):
+    """The window geometry (gh, gw, wh, ww) of a windowed attention call, checked before any launch
+    (what the launcher itself refuses, ivit_attn_win_fwd)."""
+    try:
+        gh, gw, wh, ww = (int(v) for v in win)
+    except (TypeError, ValueError):
+        raise ValueError(f"windowed attention: win must be (gh, gw, wh, ww), got {win!r}") from None
+    if gh < 1 or gw < 1 or N != 1 + gh * gw:
+        raise ValueError(f"windowed attention: N = {N} tokens is not 1 + {gh} x {gw}")
+    if wh < 1 or ww < 1:
+        raise ValueError(f"windowed attention: window {wh} x {ww} must be at least 1 x 1")
+    if wh * ww > 256:
+        raise ValueError(f"windowed attention: window {wh} x {ww} holds more than 256 tokens")
+    if qkv.shape[-1] != 3 * H * 64 or qkv.numel() != B * N * 3 * H * 64:
+        raise ValueError(f"windowed attention: qkv {tuple(qkv.shape)} is not [B*N, 3*H*64] with B = {B}, N = {N}, "
+                         f"H = {H} (head dim 64 only)")
+    return gh, gw, wh, ww
+
+
+def attn_win_fwd(qkv, B, N, H, cdt, win):
+    """attn_fwd inside windows: win = (gh, gw, wh, ww), N = 1 + gh*gw (ivit_attn_win_fwd)."""
+    gh, gw, wh, ww = _win_check(qkv, B, N, H, win)
+    out = torch.empty((B * N, H * 64), dtype=qkv.dtype, device=qkv.device)
+    lse = torch.empty((B, H, N), dtype=torch.float32, device=qkv.device)
+    ev = KernelTimer.span("attn_fwd")
+    lib.ivit_attn_win_fwd(cdt, ptr(qkv), B, N, gh, gw, wh, ww, H, 64, ptr(out), ptr(lse), stream())
+    if ev is not None:
+        ev.record()
+    return out, lse
+
+
+def attn_win_bwd(qkv, out, dout, lse, B, N, H, cdt, win):
+    gh, gw, wh, ww = _win_check(qkv, B, N, H, win)
+    dqkv = torch.empty_like(qkv)
+    ev = KernelTimer.span("attn_bwd")
+    lib.ivit_attn_win_bwd(cdt, ptr(qkv), ptr(out), ptr(dout), ptr(lse), B, N, gh, gw, wh, ww, H, 64, ptr(dqkv),
+                          stream())
+    if ev is not None:
+        ev.record()
+    return dqkv
+
+
+def attn_win_fwd_q2(qkv, B, N, H, win, skip=None):
+    """attn_fwd_q2 inside windows (ivit_attn_win_fwd_q2); skip as for attn_fwd_q2."""
+    gh, gw, wh, ww = _win_check(qkv, B, N, H, win)
+    out = torch.empty((B * N, H * 64), dtype=qkv.dtype, device=qkv.device)
+    lse = torch.empty((B, H, N), dtype=torch.float32, device=qkv.device)
+    sk = None if skip is None else _skip_check(skip, B, 1)
+    ev = KernelTimer.span("attn_fwd")
+    lib.ivit_attn_win_fwd_q2(ptr(qkv), B, N, gh, gw, wh, ww, H, 64, ptr(out), ptr(lse), ptr(sk), stream())
+    if ev is not None:
+        ev.record()
+    return out, lse
+
+
+def attn_win_bwd_q2(qkv, out, dout, lse, B, N, H, win, skip=None):
+    """attn_bwd_q2 inside windows (ivit_attn_win_bwd_q2): dqkv w.r.t. the unscaled q, k, v."""
+    gh, gw, wh, ww = _win_check(qkv, B, N, H, win)
+    dqkv = torch.empty_like(qkv)
+    sk = None if skip is None else _skip_check(skip, B, 1)
+    ev = KernelTimer.span("attn_bwd")
+    lib.ivit_attn_win_bwd_q2(ptr(qkv), ptr(out), ptr(dout), ptr(lse), B, N, gh, gw, wh, ww, H, 64, ptr(dqkv),
+                             ptr(sk), stream())
+    if ev is not None:
+        ev.record()
+    return dqkv
+
+
+def block_meta(meta):
+    """(B, N, H, cdt, eps, win) of a ViT block's meta: the 5-tuple of a global block, or with the
+    window geometry (gh, gw, wh, ww) as a sixth element (None: global)."""
+    if len(meta) == 5:
+        return (*meta, None)
+    return tuple(meta)
+
+
 def _request_index(v, hi, what):
     """A host list or a tensor of request indices -> a checked host int64 tensor (ValueError outside
     [0, hi): a bad index never reaches the device)."""
@@ -878,7 +954,7 @@ class ViTBlockPanelFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, ln_in, m_in, r_in, n1w, n1b, qkvw, qkvb, pw, pb, n2w, n2b, f1w, f1b, f2w, f2b, nxw, nxb,
                 s1, s2, meta, hand_mine=None, hand_prev=None):
-        B, N, H, _, eps = meta
+        B, N, H, _, eps, win = block_meta(meta)
         if ln_in is None:
             ln1, m1, r1 = layernorm_fwd(x, n1w, n1b, eps, torch.bfloat16)
         else:
@@ -887,7 +963,10 @@ class ViTBlockPanelFn(torch.autograd.Function):
         # of a branch which samples are dropped (factor 0): their GEMM panels and attention
         # workgroups are not computed, and what other kernels still read of them is written as zeros
         qkv, _ = panel_fwd(ln1, qkvw, qkvb, qcols=H * 64, qscale=Q2_SCALE, skip=s1, rps=N)
-        o, lse = attn_fwd_q2(qkv, B, N, H, skip=s1)
+        if win is None:
+            o, lse = attn_fwd_q2(qkv, B, N, H, skip=s1)
+        else:
+            o, lse = attn_win_fwd_q2(qkv, B, N, H, win, skip=s1)
         x1, ln2, m2, r2 = linear_resid_ln_fwd(o, pw, pb, x, s1, N, n2w, n2b, eps, skip=True)
         # inference (torch.inference_mode): nothing is saved, and fc1 skips its pre-activation copy.
         # training: h = GELU'(fc1 pre-activation) for the fc2 dgrad (panel_dgrad_mul), computed
@@ -920,7 +999,7 @@ class ViTBlockPanelFn(torch.autograd.Function):
     def backward(ctx, dx2, *_unused):
         (x, ln1, qkv, o, lse, x1, ln2, h, a, m1, r1, m2, r2, n1w, n2w, s1, s2, qkvw, f1w, f2w,
          pw) = ctx.saved_tensors
-        B, N, H, _, _ = ctx.meta
+        B, N, H, _, _, win = block_meta(ctx.meta)
         cd = torch.bfloat16
         dx2 = torch.zeros_like(x) if dx2 is None else dx2.contiguous()
         hm, hp = ctx.hand_mine, ctx.hand_prev
@@ -940,7 +1019,10 @@ class ViTBlockPanelFn(torch.autograd.Function):
         dx1, dx1s, dg2, dbe2 = linear_dgrad_ln_bwd(dh, f1w, x1, n2w, m2, r2, dres=dx2, dx=torch.empty_like(dx2),
                                                    xs_dtype=cd, row_scale=s1, rps=N, dg=dv[6], db=dv[7], skip=s2)
         do = panel_dgrad(dx1s, pw, skip=s1, rps=N)
-        dqkv = attn_bwd_q2(qkv, o, do, lse, B, N, H, skip=s1)
+        if win is None:
+            dqkv = attn_bwd_q2(qkv, o, do, lse, B, N, H, skip=s1)
+        else:
+            dqkv = attn_win_bwd_q2(qkv, o, do, lse, B, N, H, win, skip=s1)
         # qkv dgrad with norm1's backward in the epilogue
         if hp is not None:  # also the previous block's bf16(dx0 * s2) (GradHandoff)
             dx0, dx0s, dg1, dbe1 = linear_dgrad_ln_bwd(dqkv, qkvw, x, n1w, m1, r1, dres=dx1, dx=dx1, xs_dtype=cd,
@@ -969,16 +1051,16 @@ class ViTBlockFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, n1w, n1b, qkvw, qkvb, pw, pb, n2w, n2b, f1w, f1b, f2w, f2b, s1, s2, meta):
-        B, N, H, cdt, eps = meta
+        B, N, H, cdt, eps, win = block_meta(meta)
         cd = tdtype(cdt)
         wq, wp, w1, w2 = cast_weight(qkvw, cd), cast_weight(pw, cd), cast_weight(f1w, cd), cast_weight(f2w, cd)
         ln1, m1, r1 = layernorm_fwd(x, n1w, n1b, eps, cd)
         if cdt == BF16:
             qkv = qkv_fwd_q2(ln1, wq, qkvb, H * 64)
-            o, lse = attn_fwd_q2(qkv, B, N, H)
+            o, lse = attn_fwd_q2(qkv, B, N, H) if win is None else attn_win_fwd_q2(qkv, B, N, H, win)
         else:
             qkv, _ = linear_fwd(ln1, wq, qkvb, cdt)
-            o, lse = attn_fwd(qkv, B, N, H, cdt)
+            o, lse = attn_fwd(qkv, B, N, H, cdt) if win is None else attn_win_fwd(qkv, B, N, H, cdt, win)
         x1, _ = linear_fwd(o, wp, pb, cdt, resid=x, row_scale=s1, rps=N)
         ln2, m2, r2 = layernorm_fwd(x1, n2w, n2b, eps, cd)
         # inference (torch.inference_mode): nothing is saved, and fc1 skips its pre-activation copy
@@ -993,7 +1075,7 @@ class ViTBlockFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, dx2):
         x, ln1, qkv, o, lse, x1, ln2, h, a, m1, r1, m2, r2, n1w, n2w, wq, wp, w1, w2, s1, s2 = ctx.saved_tensors
-        B, N, H, cdt, _ = ctx.meta
+        B, N, H, cdt, _, win = block_meta(ctx.meta)
         cd = tdtype(cdt)
         dx2 = dx2.contiguous()
         dx2s = add_act_grad(dx2, row_scale=s2, row_elems=N * x.shape[1], out_dtype=cd)
@@ -1005,7 +1087,13 @@ class ViTBlockFn(torch.autograd.Function):
         dW1, db1 = linear_wgrad(dh, ln2, cdt)
         do = linear_dgrad(dx1s, wp, cdt, cd)
         dWp, dbp = linear_wgrad(dx1s, o, cdt)
-        dqkv = attn_bwd_q2(qkv, o, do, lse, B, N, H) if cdt == BF16 else attn_bwd(qkv, o, do, lse, B, N, H, cdt)
+        if win is not None:
+            dqkv = (attn_win_bwd_q2(qkv, o, do, lse, B, N, H, win) if cdt == BF16
+                    else attn_win_bwd(qkv, o, do, lse, B, N, H, cdt, win))
+        elif cdt == BF16:
+            dqkv = attn_bwd_q2(qkv, o, do, lse, B, N, H)
+        else:
+            dqkv = attn_bwd(qkv, o, do, lse, B, N, H, cdt)
         dln1 = linear_dgrad(dqkv, wq, cdt, torch.float32)
         dx0, _, dg1, dbe1 = layernorm_bwd(x, n1w, m1, r1, dln1, dres=dx1, dx=dx1)
         dWq, dbq = linear_wgrad(dqkv, ln1, cdt)

@@ -69,7 +69,72 @@ APPLY_INTENTION_DOWNSAMPLING = True
 USE_INTENTION_WEIGHTS = False
 
 
-def backbone_cfg(img_size=(GRID_HEIGHT_PX, GRID_WIDTH_PX)):
+def parse_window(text):
+    """'HxW' (or one number for a square window) -> (wh, ww); ValueError for anything else or a
+    window outside 1 .. 256 tokens."""
+    parts = str(text).lower().split("x")
+    try:
+        vals = [int(v) for v in parts]
+    except ValueError:
+        raise ValueError(f"--window {text!r}: expected HxW, e.g. 10x10") from None
+    if len(vals) == 1:
+        vals = vals * 2
+    if len(vals) != 2 or min(vals) < 1 or vals[0] * vals[1] > 256:
+        raise ValueError(f"--window {text!r}: expected HxW with 1 <= H*W <= 256")
+    return vals[0], vals[1]
+
+
+def parse_global_blocks(text):
+    """'i,j,...' -> a tuple of block indices (negative from the end); ValueError otherwise."""
+    try:
+        vals = tuple(int(v) for v in str(text).split(",") if v.strip() != "")
+    except ValueError:
+        raise ValueError(f"--global-blocks {text!r}: expected a comma list of block indices") from None
+    if not vals:
+        raise ValueError(f"--global-blocks {text!r}: names no block")
+    return vals
+
+
+def add_window_args(ap):
+    ap.add_argument("--window", type=str, default=None, metavar="HxW",
+                    help="windowed attention in the ViT streams: attention inside windows of H x W patches in every "
+                         "block but the global ones (ViT only; no parameter changes)")
+    ap.add_argument("--global-blocks", type=str, default=None, metavar="I,J,...",
+                    help="with --window: the blocks that keep global attention (default: the last block of each of "
+                         "four equal groups, 2,5,8,11 at depth 12)")
+
+
+def window_args(ap, args, blocks_alone=False):
+    """-> (window or None, global blocks or None) of the parsed flags; ap.error on bad values.
+    blocks_alone: --global-blocks without --window is allowed (eval_vit.py: the window then comes from
+    the checkpoint)."""
+    try:
+        win = parse_window(args.window) if args.window is not None else None
+        glob = parse_global_blocks(args.global_blocks) if args.global_blocks is not None else None
+    except ValueError as e:
+        ap.error(str(e))
+    if glob is not None and win is None and not blocks_alone:
+        ap.error("--global-blocks needs --window")
+    return win, glob
+
+
+def window_line(model):
+    """One log line: the window, the global blocks and the windows per stream."""
+    vl = model.backbone.vit_lidar
+    wh, ww = vl.window_size
+    gh, gw = vl.patch_embed.grid_size
+    nwin = -(-gh // wh) * -(-gw // ww)
+    return (f"Windowed attention: {wh}x{ww} patches, global blocks {list(vl.global_attn_indexes)}, "
+            f"{nwin} windows per stream on the {gh}x{gw} grid (+ CLS alone)")
+
+
+def backbone_cfg(img_size=(GRID_HEIGHT_PX, GRID_WIDTH_PX), window=None, global_blocks=None):
+    """``window`` / ``global_blocks``: vit_window_size / vit_global_attn_indexes, present in the
+    dict only when a window is set."""
+    win = {}
+    if window is not None:
+        win['vit_window_size'] = tuple(window)
+        win['vit_global_attn_indexes'] = None if global_blocks is None else tuple(global_blocks)
     return {
         'lidar_input_channels': LIDAR_TOTAL_CHANNELS,
         'map_input_channels': MAP_CHANNELS,
@@ -87,6 +152,7 @@ def backbone_cfg(img_size=(GRID_HEIGHT_PX, GRID_WIDTH_PX)):
         'fusion_block_kernel_size': 3,
         'fusion_block_stride': 1,
         'res_block_type': BasicBlock,
+        **win,
     }
 
 
@@ -151,7 +217,9 @@ def parse_args(argv=None):
                          "--min-lr over --epochs, stepped every update")
     ap.add_argument("--warmup-epochs", type=float, default=0.0, metavar="E", help="with --sched cosine")
     ap.add_argument("--min-lr", type=float, default=0.0, metavar="X", help="with --sched cosine")
+    add_window_args(ap)
     args = ap.parse_args(argv)
+    args.window_size, args.global_attn_indexes = window_args(ap, args)
     if not 0.0 <= args.iou_loss_weight < float("inf"):
         ap.error(f"--iou-loss-weight {args.iou_loss_weight}: must be a finite number >= 0")
     if args.layer_decay is not None and not 0.0 < args.layer_decay <= 1.0:
@@ -251,12 +319,14 @@ def main(argv=None, variant="vit"):
     if variant != "vit" and (args.pretrained_lidar is not None or args.pretrained_map is not None):
         raise SystemExit("--pretrained-lidar / --pretrained-map: IntentNetCNN has no ViT stream to load timm weights "
                          "into (use train_vit.py; --init-from works for both)")
+    if variant != "vit" and args.window_size is not None:
+        raise SystemExit("--window: IntentNetCNN has no attention to window (use train_vit.py)")
     rank, local, world, device = init_distributed()
     if device.type != "cuda":
         raise RuntimeError("train_vit.py runs on the MI355X kernels: no ROCm GPU visible")
     H, W = (int(v) for v in args.grid.lower().split("x"))
     if variant == "vit":
-        cfg = backbone_cfg((H, W))
+        cfg = backbone_cfg((H, W), args.window_size, args.global_attn_indexes)
         stride = int(cfg['vit_model_name_lidar'].split('_patch')[-1].split('_')[0]) * cfg.get('fusion_block_stride', 1)
     else:
         cfg, stride = cnn_backbone_cfg(), FEATURE_MAP_STRIDE_CNN
@@ -294,6 +364,8 @@ def main(argv=None, variant="vit"):
 
     if variant == "vit":
         model = IntentNetViT(backbone_cfg=cfg).to(device)
+        if args.window_size is not None:
+            log(window_line(model))
     else:
         from model_cnn import IntentNetCNN
         model = IntentNetCNN(backbone_cfg=cfg).to(device)

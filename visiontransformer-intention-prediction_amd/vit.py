@@ -52,9 +52,49 @@ class Mlp(nn.Module):
         self.fc2 = Linear(hidden, dim)
 
 
+def _window_pair(window_size):
+    """(wh, ww) of a window_size argument: None, one int (square) or a pair; at most 256 tokens."""
+    if window_size is None:
+        return None
+    if isinstance(window_size, int):
+        window_size = (window_size, window_size)
+    try:
+        wh, ww = (int(v) for v in window_size)
+    except (TypeError, ValueError):
+        raise ValueError(f"window_size must be None, an int or (wh, ww), got {window_size!r}") from None
+    if wh < 1 or ww < 1 or wh * ww > 256:
+        raise ValueError(f"window_size {wh} x {ww}: a window holds 1 to 256 tokens")
+    return wh, ww
+
+
+def default_global_attn_indexes(depth):
+    """ViTDet's rule (Li et al. 2022): the last block of each of four equal groups stays global,
+    (2, 5, 8, 11) at depth 12. Shallower streams than four blocks keep their last block global."""
+    if depth < 4:
+        return (depth - 1,)
+    return tuple((i + 1) * depth // 4 - 1 for i in range(4))
+
+
+def resolve_global_attn_indexes(depth, indexes):
+    """The sorted block indices that keep global attention: ``indexes`` (negative from the end;
+    outside [-depth, depth) raises), or the default rule when None."""
+    if indexes is None:
+        return default_global_attn_indexes(depth)
+    out = set()
+    for i in indexes:
+        i = int(i)
+        if i < -depth or i >= depth:
+            raise ValueError(f"global_attn_indexes: block {i} outside a depth-{depth} stream")
+        out.add(i + depth if i < 0 else i)
+    return tuple(sorted(out))
+
+
 class Block(nn.Module):
-    def __init__(self, dim, num_heads, mlp_ratio, drop_path):
+    def __init__(self, dim, num_heads, mlp_ratio, drop_path, window_size=None):
         super().__init__()
+        # attention mode: None = global; (wh, ww) = inside windows of wh x ww patches tiling the
+        # stream's patch grid from its top-left corner (ops.attn_win_*); assignable
+        self.window_size = _window_pair(window_size)
         self.norm1 = LayerNorm(dim, eps=1e-6)
         self.attn = Attention(dim, num_heads)
         self.norm2 = LayerNorm(dim, eps=1e-6)
@@ -85,16 +125,24 @@ class Block(nn.Module):
         self.last_scales = (s[0].contiguous(), s[1].contiguous())
         return self.last_scales
 
-    def forward_flat(self, x, B, N, cdt, ln_in=None, next_norm=None, hand_mine=None, hand_prev=None, drawn=None):
+    def forward_flat(self, x, B, N, cdt, ln_in=None, next_norm=None, hand_mine=None, hand_prev=None, drawn=None,
+                     grid=None):
         """-> (x_out, (y, mean, rstd) of the next block's norm1, empty tensors without `next_norm`,
         None on the engine path). Row-panel path (ops.ViTBlockPanelFn) only: `ln_in` is this
         block's (y, mean, rstd) of norm1 computed by the previous block's fc2 epilogue; `next_norm`
-        the next block's norm1, whose forward this block's fc2 epilogue runs; the hand-offs."""
+        the next block's norm1, whose forward this block's fc2 epilogue runs; the hand-offs.
+        ``grid``: the stream's patch grid (gh, gw), which a windowed block needs (N = 1 + gh*gw)."""
         s1, s2 = self._scales(B, x.device, drawn)
         params = (self.norm1.weight, self.norm1.bias, self.attn.qkv.weight, self.attn.qkv.bias,
                   self.attn.proj.weight, self.attn.proj.bias, self.norm2.weight, self.norm2.bias,
                   self.mlp.fc1.weight, self.mlp.fc1.bias, self.mlp.fc2.weight, self.mlp.fc2.bias)
         meta = (B, N, self.attn.num_heads, cdt, 1e-6)
+        if self.window_size is not None:
+            if grid is None or N != 1 + int(grid[0]) * int(grid[1]):
+                raise ValueError(f"windowed block (window_size {self.window_size}): needs the patch grid of its "
+                                 f"{N} tokens (got grid {grid})")
+            wh, ww = _window_pair(self.window_size)
+            meta = meta + ((int(grid[0]), int(grid[1]), wh, ww),)
         if not ops.block_on_panel(cdt, x.shape[1]):
             return ops.ViTBlockFn.apply(x, *params, s1, s2, meta), None
         nxw = next_norm.weight if next_norm is not None else None
@@ -111,7 +159,7 @@ class Block(nn.Module):
 
 class VisionTransformer(nn.Module):
     def __init__(self, img_size=(224, 224), patch_size=8, in_chans=3, embed_dim=384, depth=12, num_heads=6,
-                 mlp_ratio=4.0, drop_path_rate=0.0):
+                 mlp_ratio=4.0, drop_path_rate=0.0, window_size=None, global_attn_indexes=None):
         super().__init__()
         self.embed_dim = self.num_features = embed_dim
         self.num_prefix_tokens = 1
@@ -120,7 +168,14 @@ class VisionTransformer(nn.Module):
         self.cls_token = nn.Parameter(torch.zeros(1, 1, embed_dim))
         self.pos_embed = nn.Parameter(torch.randn(1, n_tok, embed_dim) * 0.02)
         dpr = [x.item() for x in torch.linspace(0, drop_path_rate, depth)]
-        self.blocks = nn.ModuleList([Block(embed_dim, num_heads, mlp_ratio, dpr[i]) for i in range(depth)])
+        # windowed attention (ViTDet): every block but the global ones attends inside windows; no
+        # parameters, no state_dict keys. window_size=None: every block global
+        self.window_size = _window_pair(window_size)
+        self.global_attn_indexes = (resolve_global_attn_indexes(depth, global_attn_indexes)
+                                    if self.window_size is not None else None)
+        win = [None if self.window_size is None or i in self.global_attn_indexes else self.window_size
+               for i in range(depth)]
+        self.blocks = nn.ModuleList([Block(embed_dim, num_heads, mlp_ratio, dpr[i], win[i]) for i in range(depth)])
         self.norm = LayerNorm(embed_dim, eps=1e-6)
         self.head = nn.Identity()
         nn.init.normal_(self.cls_token, std=1e-6)
@@ -151,6 +206,10 @@ class VisionTransformer(nn.Module):
 
     def _cdt(self):
         return BF16 if self.compute_dtype == torch.bfloat16 else F32
+
+    def windowed_blocks(self):
+        """Indices of the blocks that run windowed attention (Block.window_size is not None)."""
+        return [i for i, blk in enumerate(self.blocks) if blk.window_size is not None]
 
     def load_pretrained(self, path_or_state_dict, old_grid=None):
         """Load a timm checkpoint of this architecture (a ``.pth`` / ``.bin`` / ``.pt`` file through
@@ -223,6 +282,7 @@ class VisionTransformer(nn.Module):
               self.cls_token, cdt)
         t = ops.PatchEmbedFn.apply(*pe, hand_pe) if p8 else ops.PatchEmbedGenericFn.apply(*pe)
         N = self.patch_embed.num_patches + 1
+        grid = tuple(self.patch_embed.grid_size)  # read at call time: set_input_size moves it
         ln = None
         drawn = self._draw_drop_path(B, x.device)
         yield
@@ -231,7 +291,7 @@ class VisionTransformer(nn.Module):
             t, nxt_ln = blk.forward_flat(t, B, N, cdt, ln_in=ln, next_norm=nxt,
                                          hand_mine=hands[i] if hands else None,
                                          hand_prev=(hands[i - 1] if i > 0 else hand_pe) if hands else None,
-                                         drawn=drawn[i] if drawn is not None else None)
+                                         drawn=drawn[i] if drawn is not None else None, grid=grid)
             ln = nxt_ln if nxt is not None else None
             yield
         return t
@@ -254,6 +314,12 @@ class VisionTransformer(nn.Module):
         want = [b + depth if b < 0 else b for b in blocks]
         if any(b < 0 or b >= depth for b in want):
             raise ValueError(f"attention_rows: blocks {blocks} outside a depth-{depth} stream")
+        windowed = [b for b in want if self.blocks[b].window_size is not None]
+        if windowed:
+            # the rows kernel computes global softmax rows, which a windowed block never forms
+            glob = [i for i, blk in enumerate(self.blocks) if blk.window_size is None]
+            raise ValueError(f"attention_rows: block(s) {windowed} run windowed attention "
+                             f"(window {self.blocks[windowed[0]].window_size}); global blocks available: {glob}")
         B, C, H, W = x.shape
         if (H, W) != self.patch_embed.img_size:
             raise ValueError(f"Input size {(H, W)} != model img_size {self.patch_embed.img_size} (timm strict size)")
@@ -290,7 +356,8 @@ class VisionTransformer(nn.Module):
                     if i == max(want):
                         break  # nothing reads the residual stream past the last requested block
                     nxt = self.blocks[i + 1].norm1 if fuse else None
-                    t, nxt_ln = blk.forward_flat(t, B, N, cdt, ln_in=ln, next_norm=nxt)
+                    t, nxt_ln = blk.forward_flat(t, B, N, cdt, ln_in=ln, next_norm=nxt,
+                                                 grid=tuple(self.patch_embed.grid_size))
                     ln = nxt_ln if nxt is not None else None
         finally:
             for blk, (tr, ls) in zip(self.blocks, saved):
@@ -444,16 +511,18 @@ def _pretrained_file(model_name, overlay):
 
 
 def create_model(model_name, pretrained=False, in_chans=3, img_size=(224, 224), drop_path_rate=0.0,
-                 pretrained_cfg_overlay=None, **_):
+                 pretrained_cfg_overlay=None, window_size=None, global_attn_indexes=None, **_):
     """timm.create_model surface used by the reference (model_vit.py:64,71). ``pretrained=True``
     loads a timm checkpoint of ``model_name`` from a local file (_pretrained_file) through
     VisionTransformer.load_pretrained: pos_embed resampled onto ``img_size``'s grid, the 3-channel
-    patch weights adapted to ``in_chans``."""
+    patch weights adapted to ``in_chans``. ``window_size`` / ``global_attn_indexes``: windowed
+    attention in every block but the global ones (VisionTransformer); no state_dict key changes."""
     a = VIT_ARCH[model_name]
     file = _pretrained_file(model_name, pretrained_cfg_overlay) if pretrained else None
     m = VisionTransformer(img_size=img_size, patch_size=a["patch"], in_chans=in_chans, embed_dim=a["embed_dim"],
                           depth=a["depth"], num_heads=a["num_heads"], mlp_ratio=a["mlp_ratio"],
-                          drop_path_rate=drop_path_rate)
+                          drop_path_rate=drop_path_rate, window_size=window_size,
+                          global_attn_indexes=global_attn_indexes)
     if file is not None:
         m.load_pretrained(file)
     return m
